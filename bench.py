@@ -11,14 +11,31 @@ decomposition: contiguous halo rows over RCCL/xGMI).
     python bench.py                                  # 1 GPU
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 \
         --master-addr 127.0.0.1 --master-port 29500 bench.py --gpus 8
+    python bench.py --full                           # + verification (and the
+                                                     #   multi-GPU explanation)
+    python bench.py --dump-outputs DIR               # + DIR/grid.npy
+
+A plain run does only what the headline figure needs: set-up (multi-GPU: the
+autotune that picks the benchmarked layout), warmup, the timed steps, the
+output dump if asked for, the JSON line.  The verification run and the
+multi-GPU explanation below are runs of their own and happen with `--full`
+only ("verified" is null in a plain run's JSON line).
 
 Data: synthetic random-init temperature grid (--init random), no files.
 Timing: W untimed warmup steps, then barrier + synchronize, K timed steps,
 synchronize + barrier; the max over ranks is reported.  Everything the model
 does per iteration (halo exchange, all kernels) is inside the timed region.
 
-Verification (after the timed region, `--no-verify` skips it): the global
-checksum of the final state is compared with the same number of steps of a
+Outputs (`--dump-outputs DIR`, after the timed region): rank 0 writes
+DIR/grid.npy, the float32 temperature field after the last timed step as
+HeatSolver.gather() returns it.  A field above 48 MB is sampled by rows: a
+sorted row subset drawn with a fixed seed from (nx, ny) alone, all columns
+(8192^2: 1464 of the 8192 rows); DIR/grid_rows.npy holds the row indices
+(float64).  The initial condition is seeded (1234), so two builds run with the
+same arguments write comparable files.
+
+Verification (`--full`; after the timed region, `--no-verify` skips it): the
+global checksum of the final state is compared with the same number of steps of a
 single-rank run of the independent LDS-tiled single-step kernel on rank 0's GPU
 (bitwise-equal numerics): `"verified": true` in the JSON line means the
 benchmarked (multi-GPU, graph-captured, temporally blocked) run computed
@@ -34,8 +51,8 @@ best) is timed on the real ranks (max over ranks) and the fastest is
 benchmarked; the table is in the JSON line ("autotune", the ruled-out ones
 in "autotune_pruned") and the choice in config.parallelism.
 
-Multi-GPU explanation (after verification, untimed): "predicted" is the
-model's time per 1000 iterations and node Tcells/s for the chosen layout
+Multi-GPU explanation (`--full`; after verification, untimed): "predicted" is
+the model's time per 1000 iterations and node Tcells/s for the chosen layout
 (per-rank plate rate measured on one GPU + a stated xGMI exchange model,
 parameters in "model"), and "phase_seconds_per_1000" the per-rank exchange /
 compute / reduce device time of one eager phase-timed run of the same
@@ -73,10 +90,12 @@ import sys
 import tempfile
 import time
 
+import numpy as np
 import torch
 import torch.distributed as dist
 
 BASELINE_MCELLS = 3556.2  # reference best single-GPU throughput (Heat.pdf p.11 Table 6, 1000^2 T=8)
+DUMP_BYTES = 48 * 10**6  # --dump-outputs: larger fields are sampled by rows
 METRIC = "Mcells/sec (whole node) + sec/1000 iters, 8192^2 grid at 1/2/4/8 MI355X"
 
 
@@ -100,6 +119,23 @@ def rccl_links(path: str) -> list:
     except OSError:
         return []
     return sorted(seen)
+
+
+def dump_outputs(solver, out_dir: str, rank: int) -> None:
+    """DIR/grid.npy: the field the timed path left after its last step, as a
+    caller gets it from HeatSolver.gather() (collective; rank 0 writes).  A
+    field above DUMP_BYTES keeps a seeded, sorted subset of its rows."""
+    grid = solver.gather()
+    if rank != 0:
+        return
+    os.makedirs(out_dir, exist_ok=True)
+    nx, ny = grid.shape
+    keep = max(1, DUMP_BYTES // (ny * grid.itemsize))
+    if keep < nx:
+        rows = np.sort(np.random.default_rng([nx, ny]).choice(nx, size=keep, replace=False))
+        grid = grid[rows]
+        np.save(os.path.join(out_dir, "grid_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(out_dir, "grid.npy"), np.ascontiguousarray(grid, dtype=np.float32))
 
 
 def main() -> int:
@@ -137,8 +173,15 @@ def main() -> int:
     ap.add_argument("--halo-passes", type=int, default=0)
     ap.add_argument("--phase-timing", action="store_true",
                     help="diagnostic: eager run with per-phase device times (not the headline)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the verification "
+                         "against a single-rank LDS-kernel run and, multi-GPU, the model "
+                         "prediction with one phase-timed run")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the field after the last timed step to DIR/grid.npy (float32; "
+                         "a seeded row sample of a field above 48 MB, rows in grid_rows.npy)")
     ap.add_argument("--no-verify", action="store_true",
-                    help="skip the post-run check against a single-rank LDS-kernel run")
+                    help="--full: skip the post-run check against a single-rank LDS-kernel run")
     ap.add_argument("--allow-fallback", action="store_true",
                     help="if RCCL fails on every rank, run with host-staged halos over gloo")
     ap.add_argument("--no-autotune", action="store_true",
@@ -352,13 +395,16 @@ def main() -> int:
             return 1
     elapsed, done, phases = res
 
+    if args.dump_outputs:
+        watchdog("dump", args.watchdog_s)
+        dump_outputs(solver, args.dump_outputs, rank)
     verified = None
     check = {}
-    if not args.no_verify:
+    if args.full and not args.no_verify:
         watchdog("verify", args.watchdog_s)
         verified, check = verify(solver, cfg, rank, world, device, HeatSolver, DistInfo)
     explain = None
-    if world > 1:
+    if args.full and world > 1:
         # Untimed: the model's prediction for the chosen layout and the
         # measured per-rank phase split of one eager phase-timed run.
         watchdog("explain", args.watchdog_s)

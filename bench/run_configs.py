@@ -60,6 +60,9 @@ def run(cmd, timeout=3000):
 
 
 def bench(n, args):
+    # --full: the recorded lines carry the verification (and, multi-GPU, the
+    # model's prediction and the phase split).
+    args = ["--full"] + args
     if n == 1:
         return [sys.executable, "bench.py"] + args
     return [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={n}",

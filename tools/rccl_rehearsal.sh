@@ -1,5 +1,5 @@
 #!/bin/bash
-# Multi-rank RCCL rehearsal on ONE GPU: bench.py as N torchrun ranks that all
+# Multi-rank RCCL rehearsal on ONE GPU: bench.py --full as N torchrun ranks that all
 # use device 0.  Each rank claims its own RCCL host id (HEAT_RCCL_HOST_PER_RANK,
 # see bench.py), so RCCL's duplicate-GPU check passes and the ranks exchange
 # over the socket transport on loopback.  Everything else is the multi-GPU
@@ -19,7 +19,7 @@ for n in $NS; do
   port=$((port + 7))
   echo "== $n ranks"
   timeout -k 10 300 python -m torch.distributed.run --nnodes=1 --nproc-per-node "$n" \
-      --master-addr 127.0.0.1 --master-port $port bench.py --gpus "$n" --verbose "$@" \
+      --master-addr 127.0.0.1 --master-port $port bench.py --gpus "$n" --full --verbose "$@" \
       > gpurun_out/rccl_rehearsal_n$n.json 2> gpurun_out/rccl_rehearsal_n$n.err
   rc=$?
   cat gpurun_out/rccl_rehearsal_n$n.json
