@@ -7,9 +7,18 @@ Mirrors the reference programs' semantics:
   * the convergence test every C steps (``cuda/cuda_heat.cu:219-236``,
     ``mpi/...c:235-262``) with the canonical / mpi / cuda schedules.
 
-The update here is evaluated in plain float32 (NumPy has no fused
-multiply-add); the native engine evaluates the same expression with FMA, so
-the two agree to within a few float32 ulps per step, not bitwise.
+Three evaluations of the update:
+  * ``step_np`` / ``step_torch``: plain float32, every operation rounded on
+    its own.  The native engine contracts the expression into FMAs, so these
+    agree with it to within a few float32 ulps per step, not bitwise.
+  * ``step_np_fma``: the engine's default numerics (``heat::stencil``,
+    csrc/include/heat/init_fn.hpp) bit for bit.  NumPy has no fused
+    multiply-add; ``fma32`` emulates a correctly rounded fp32 one in float64
+    (exact product, TwoSum error term, round-to-odd, one rounding to fp32).
+    It shares no code with the engine, so it is the independent exact oracle
+    of every kernel and backend (``run_np(numerics="fma")``).
+  * ``step_np_mpi``: the reference MPI program's double arithmetic
+    (``numerics="mpi"``), exact as well.
 """
 from __future__ import annotations
 
@@ -73,6 +82,57 @@ def step_np(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
     return out
 
 
+def fma32(a, b, c) -> np.ndarray:
+    """Correctly rounded float32 fused multiply-add ``a * b + c`` on arrays
+    (what C's ``fmaf`` and the GPU's ``v_fma_f32`` compute, subnormals kept).
+
+    The float64 product of two float32 values is exact (48 significant bits,
+    exponents within range).  Adding ``c`` in float64 rounds once; rounding
+    that sum to float32 would round twice and go wrong near float32 ties.  So
+    the sum is first forced to round-to-odd: TwoSum gives the exact error of
+    the float64 addition, and an inexact sum with an even last mantissa bit is
+    moved to its odd neighbour on the side of the error.  A round-to-odd value
+    with >= 2 bits more than the target format rounds to the target exactly as
+    the infinitely precise sum would (float64 has 29 more than float32, and
+    still more where the float32 result is subnormal)."""
+    a = np.asarray(a, np.float32).astype(np.float64)
+    b = np.asarray(b, np.float32).astype(np.float64)
+    c = np.asarray(c, np.float32).astype(np.float64)
+    with np.errstate(invalid="ignore", over="ignore"):
+        p = a * b
+        s = p + c
+        bb = s - p                       # TwoSum (Knuth): s + err == p + c exactly
+        err = (p - (s - bb)) + (c - bb)
+        s, err = np.broadcast_arrays(s, err)
+        even = (s.view(np.int64) & 1) == 0
+        fix = (err != 0) & np.isfinite(s) & even   # inf / NaN sums pass through
+        toward = np.where(err > 0, np.inf, -np.inf)
+        s = np.where(fix, np.nextafter(s, toward), s)
+        return s.astype(np.float32)
+
+
+def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
+    """One step with the engine's default numerics, bit for bit: the
+    expression of ``heat::stencil`` with the same operands in the same order,
+        tx = fma(-2, c, s + n);  ty = fma(-2, c, e + w)
+        u' = fma(cy, ty, fma(cx, tx, c))
+    (n / s: rows above / below, w / e: columns left / right; cx and cy rounded
+    to float32 first, as HeatParams carries them); boundary ring unchanged."""
+    u = np.asarray(u, np.float32)
+    out = u.copy()
+    if u.shape[0] < 3 or u.shape[1] < 3:
+        return out
+    c = u[1:-1, 1:-1]
+    with np.errstate(over="ignore", invalid="ignore"):
+        ns = u[2:, 1:-1] + u[:-2, 1:-1]     # s + n, float32
+        ew = u[1:-1, 2:] + u[1:-1, :-2]     # e + w, float32
+    m2 = np.float32(-2.0)
+    tx = fma32(m2, c, ns)
+    ty = fma32(m2, c, ew)
+    out[1:-1, 1:-1] = fma32(np.float32(cy), ty, fma32(np.float32(cx), tx, c))
+    return out
+
+
 def step_np_mpi(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
     """One step with the reference MPI program's arithmetic
     (mpi/mpi_heat_improved_persistent_stat.c:168-174): the two neighbour sums
@@ -117,8 +177,10 @@ def run_np(nx: int, ny: int, steps: int, cx: float = 0.1, cy: float = 0.1,
            compat: str = "none", init: str = "ref-wrap", seed: int = 0,
            u0: Optional[np.ndarray] = None,
            numerics: str = "fp32") -> Tuple[np.ndarray, int, int]:
-    """Run the model; returns (grid, steps_done, converged_at or -1)."""
-    step = step_np_mpi if numerics == "mpi" else step_np
+    """Run the model; returns (grid, steps_done, converged_at or -1).
+    numerics: "fp32" (plain float32, a few ulps from the engine), "fma" (the
+    engine's default numerics, exact) or "mpi" (its numerics="mpi", exact)."""
+    step = {"fp32": step_np, "fma": step_np_fma, "mpi": step_np_mpi}[numerics]
     u = init_grid(nx, ny, init, seed) if u0 is None else np.array(u0, np.float32)
     total = steps + 1 if compat == "mpi" else steps
     checks = set(check_points(total, check_interval, compat)) if converge else set()
