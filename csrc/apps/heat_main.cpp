@@ -55,6 +55,8 @@ void usage() {
       "  --schedule auto|sync|overlap|pipeline   multi-rank pass schedule [auto=sync]\n"
       "  --halo-passes M         sync schedule: passes per halo exchange [auto]\n"
       "  --numerics fp32|mpi     update arithmetic (mpi = reference MPI double) [fp32]\n"
+      "  --insulated SIDES       insulated (zero-flux) plate edges: any of n s w e (n = row 0,\n"
+      "                          w = column 0), or all; the others keep their temperature []\n"
       "  --checkpoint PATH --checkpoint-every K   periodic binary checkpoints\n"
       "  --resume PATH           start from a binary checkpoint\n"
       "  --transport auto|local|tcp|rccl|loopback inter-rank transport  [auto]\n"
@@ -240,14 +242,15 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
           "\"mcells_per_s\": %.3f, \"s_per_1000_iters\": %.6f, \"converged\": %s, "
           "\"converged_at\": %lld, \"last_resid\": %.6g, \"passes\": %lld, \"exchanges\": %lld, "
           "\"transport\": \"%s\", \"schedule\": \"%s\", \"halo\": %d, \"t_exchange\": %.6f, "
-          "\"t_compute\": %.6f, \"t_reduce\": %.6f}\n",
+          "\"t_compute\": %.6f, \"t_reduce\": %.6f, \"insulated\": \"%s\"}\n",
           (long long)P.nx, (long long)P.ny, (long long)total, (long long)acc.steps_done, world,
           P.backend == Backend::Hip ? "hip" : "cpu", c.px, c.py, S.tb_depth(), secs,
           secs > 0 ? cells / secs / 1e6 : 0.0,
           acc.steps_done > 0 ? secs * 1000.0 / double(acc.steps_done) : 0.0,
           acc.converged ? "true" : "false", (long long)acc.converged_at, double(acc.last_resid),
           (long long)acc.passes, (long long)acc.exchanges, S.transport().name(),
-          schedule_name(S.schedule()), S.halo(), acc.t_exchange, acc.t_compute, acc.t_reduce);
+          schedule_name(S.schedule()), S.halo(), acc.t_exchange, acc.t_compute, acc.t_reduce,
+          insulated_name(P.insulated).c_str());
     }
     std::fflush(stdout);
   }
@@ -343,6 +346,14 @@ int main(int argc, char** argv) {
     else if (a == "--warmup") o.warmup = std::atoll(need().c_str());
     else if (a == "--gpus") gpus = std::atoi(need().c_str());
     else if (a == "--phase-timing") P.phase_timing = true;
+    else if (a == "--insulated") {
+      const std::string s = need();
+      if (!parse_insulated(s, &P.insulated)) {
+        std::fprintf(stderr, "heat: --insulated %s: expected \"all\" or any of the letters nswe "
+                     "(n = row 0, s = last row, w = column 0, e = last column)\n", s.c_str());
+        return 2;
+      }
+    }
     else if (a == "--plan") plan = true;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 2; }
   }
@@ -363,16 +374,21 @@ int main(int argc, char** argv) {
     // gfx950 resident fit: whether every rank's span box runs as one-round
     // resident tiles.
     auto shape = [&](const Box& b) { return resident_shape_static(b, depth); };
+    // Insulated sides have ghosts too: a one-rank plate with one gets the
+    // multi-rank halo depth, and along such an axis a block lends rows 1..H.
+    const bool ghosts = ranks > 1 || P.insulated != 0;
+    const int64_t ext = halo_extent_limit(cart, P.nx, P.ny, P.insulated);
     int m = 1;
-    if (ranks > 1) {
-      const int rm = resident_halo_passes(cart, P.nx, P.ny, depth, 8, shape);
+    if (ghosts) {
+      const int rm = resident_halo_passes(cart, P.nx, P.ny, depth, 8, shape, P.insulated);
       m = P.halo_passes > 0 ? P.halo_passes : rm >= kResMinPasses ? rm : 8;
+      if (P.insulated != 0) m = int(std::max<int64_t>(1, std::min<int64_t>(m, ext / depth)));
     }
     bool resident = true;
     int res_rows = 0, res_waves = 0;
     for (int r = 0; r < ranks; ++r) {
       const Block b = make_block(cart, r, P.nx, P.ny);
-      const int sh = shape(ranks > 1 ? span_box(cart, b, depth, m) : Box{0, b.lx, 0, b.ly});
+      const int sh = shape(ghosts ? span_box(cart, b, depth, m, P.insulated) : Box{0, b.lx, 0, b.ly});
       resident = resident && sh != 0;
       if (r == 0) res_rows = sh >> 8, res_waves = sh & 255;
     }
@@ -382,6 +398,7 @@ int main(int argc, char** argv) {
       int64_t h = int64_t(depth) * m;
       if (cart.px > 1) h = std::min<int64_t>(h, b.lx);
       if (cart.py > 1) h = std::min<int64_t>(h, b.ly);
+      if (P.insulated != 0) h = std::min<int64_t>(h, ext);
       const Layout L = Layout::make(b.lx, b.ly, int(std::max<int64_t>(1, h)));
       int64_t bytes = 2 * L.bytes();
       // Resident workgroup tiles (blocks under 64 strip-rows per SIMD on the

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define HEAT_ABI_VERSION 5
+#define HEAT_ABI_VERSION 6
 
 typedef struct heat_params {
   int64_t nx, ny;
@@ -39,6 +39,7 @@ typedef struct heat_params {
   int32_t halo_passes; /* sync schedule: passes per exchange (0 = auto) */
   int32_t numerics;    /* 0 fp32 (canonical FMA), 1 mpi (reference MPI double arithmetic) */
   int32_t phase_timing;/* 1: per-phase times in heat_run_stats (disables graphs) */
+  int32_t insulated;   /* insulated (zero-flux) plate edges: 1 north, 2 south, 4 west, 8 east */
 } heat_params;
 
 /* Transport selection for heat_solver_create. */
@@ -77,7 +78,7 @@ typedef struct heat_block_info {
   int32_t hx, hy, halo, tb_depth;
   int64_t bytes_per_field;
   int32_t schedule; /* effective heat::Schedule (1 sync, 2 overlap, 3 pipeline) */
-  int32_t pad_;
+  int32_t insulated; /* the run's insulated plate edges (heat_params.insulated) */
 } heat_block_info;
 
 typedef struct heat_checksum {
@@ -208,6 +209,13 @@ int heat_op_unpack(const float* buf, float* origin, int64_t pitch, int64_t r0, i
                    int64_t c0, int64_t c1, void* stream);
 int heat_op_residual(const float* a, const float* b, int64_t pitch, int64_t r0, int64_t r1,
                      int64_t c0, int64_t c1, unsigned* resid, void* stream);
+/* Mirror an lx x ly field into its `depth`-deep ghost frame beyond the insulated
+   sides in `sides` (1 north, 2 south, 4 west, 8 east): the device kernel, and
+   its host twin on host memory. */
+int heat_op_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
+                                  int depth, void* stream);
+int heat_cpu_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                                   int sides, int depth);
 int heat_layout(int64_t lx, int64_t ly, int halo, int64_t* pitch, int64_t* rows, int* hx,
                 int* hy);
 int heat_tb_supported(int depth);

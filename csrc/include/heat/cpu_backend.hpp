@@ -30,6 +30,11 @@ void init_field(float* origin, const Layout& L, int64_t gx0, int64_t gy0, int64_
 // NaN if any cell became NaN) when want_resid, else 0.
 float step(const float* src, float* dst, const Geom& g, const Box& box, bool want_resid);
 
+// Host twin of gpu::fill_insulated_ghosts (kernels.hpp): mirror the field
+// into the `depth`-deep ghost frame beyond the insulated sides in `sides`.
+void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
+                           int depth);
+
 void copy_box(const float* src, int64_t src_pitch, float* dst, int64_t dst_pitch, const Box& box);
 
 }  // namespace heat::cpu

@@ -23,7 +23,10 @@ namespace heat::gpu {
 // cell (0,0) of a field allocated with some Layout; (gx0, gy0) are the
 // global coordinates of that cell.  Only cells with 1 <= gx <= nx-2 and
 // 1 <= gy <= ny-2 are updated (fixed Dirichlet ring); every other
-// cell keeps its value.
+// cell keeps its value.  Insulated plate edges (Params::insulated) reach the
+// kernels only through this geometry: the solver hands them a plate extended
+// by its ghost depth beyond every insulated side (Solver::geom), whose ghost
+// cells fill_insulated_ghosts keeps equal to the plate's mirror image.
 struct StencilGeom {
   int64_t pitch = 0;
   int64_t gx0 = 0, gy0 = 0;
@@ -244,6 +247,20 @@ struct BoxCopy {
 void copy_boxes(float* origin, int64_t pitch, const BoxCopy* copies, int n, bool to_buf,
                 hipStream_t st);
 void unpack_box(const float* buf, float* origin, int64_t pitch, const Box& box, hipStream_t st);
+
+// Insulated (zero-flux) plate edges (ghost_fill.hip): in ONE launch, fill the
+// ghost frame [-depth, lx+depth) x [-depth, ly+depth) of a field beyond every
+// side in `sides` (bit 1 << heat::Dir: this rank's insulated plate edges)
+// with the mirror image of the field across that edge row / column, the edge
+// cell itself not repeated: (r < 0, c) := (-r, c), (r >= lx, c) :=
+// (2(lx-1) - r, c), likewise for columns, both reflections for a cell beyond
+// two insulated sides.  Only cells beyond at least one side of `sides` are
+// written; a source is never a target, but it may be a ghost cell that a real
+// neighbour's halo filled, so this runs after the exchange's unpack on the
+// same stream.  Needs lx > depth (ly > depth) along an axis with a side in
+// `sides` and a ghost ring at least `depth` deep.  Graph-capturable.
+void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
+                           int depth, hipStream_t st);
 
 // Order-independent checksum of the owned block, accumulated on the device
 // into out (zeroed by the caller): hash (u64, wrapping sum of

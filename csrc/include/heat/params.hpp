@@ -96,7 +96,16 @@ struct Params {
   int halo_passes = 0;      // passes per exchange with Sync (ghost depth m*K); 0 = auto
   Numerics numerics = Numerics::Fp32;
   bool phase_timing = false;  // per-phase device times in RunStats (runs eagerly)
+  // Insulated (zero-flux) plate edges, one bit per heat::Dir (1 north = row 0,
+  // 2 south, 4 west = column 0, 8 east); a clear bit is the fixed-temperature
+  // (Dirichlet) edge of the reference.  See kInsulatedAll.
+  uint8_t insulated = 0;
 };
+
+constexpr uint8_t kInsulatedAll = 15;
+// "" | any subset of "nswe" | "all" -> Params::insulated; false on a bad letter.
+bool parse_insulated(const std::string& s, uint8_t* out);
+std::string insulated_name(uint8_t mask);  // "" or the letters in n, s, w, e order
 
 const char* init_mode_name(InitMode m);
 const char* kernel_name(KernelKind k);

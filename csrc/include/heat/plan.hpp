@@ -14,8 +14,10 @@ namespace heat {
 // The first box of a resident span after an exchange of H = m * depth deep
 // halos: rank b's owned block grown by H - depth rows (columns: rounded down
 // to 4) on every side with a neighbour along a decomposed axis, as
-// Solver::resident_span tracks ghost validity.
-Box span_box(const Cart& cart, const Block& b, int depth, int m);
+// Solver::resident_span tracks ghost validity.  `insulated`
+// (Params::insulated): an insulated plate edge counts as a neighbour, and an
+// axis with one as decomposed.
+Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated = 0);
 
 // A resident tile plan's shape as one int: rows per wave << 8 | waves per
 // workgroup (0: the box has no one-round resident plan).
@@ -41,7 +43,13 @@ constexpr int kResMinPasses = 4;
 //   8192^2 on 2 x 2: m = 5 (4144^2, 20 x 16) 4.73, m = 8 (4180^2, split
 //     pipelines) 3.79.
 int resident_halo_passes(const Cart& cart, int64_t nx, int64_t ny, int depth, int mmax,
-                         const std::function<int(const Box&)>& shape);
+                         const std::function<int(const Box&)>& shape, unsigned insulated = 0);
+
+// Rows (columns) a rank can lend to an H-deep halo along each axis: the
+// smallest block extent of any rank along a decomposed axis, one less along
+// an axis with an insulated side (its ghosts mirror rows 1..H); INT64_MAX
+// along an axis with neither.  The ghost depth is at most the smaller one.
+int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated);
 
 // Host-side resident plan of a box at `depth` on an MI355X (`cus` CUs): the
 // tile planner's shapes and choice (tb_resident.hip plan_res: the lowest

@@ -18,6 +18,12 @@
 //     interior box on a high-priority comm stream: exchange-first or
 //     boundary-first.  Measured slower on MI355X at the strong-scaling shapes
 //     (see params.hpp), kept selectable and tested.
+//   * Insulated plate edges (Params::insulated) ride on the same machinery:
+//     an insulated side is a side with a neighbour whose data is the rank's
+//     own mirror image.  Its ghosts are refilled by every exchange (one
+//     fill_insulated_ghosts launch after the unpack; the whole exchange in a
+//     world of one), the pass boxes grow toward it, and the stencil kernels
+//     get a plate extended by H beyond it (geom()), so none of them changes.
 //   * Segments between convergence checks are captured once into a hipGraph
 //     per (length, parity, ghost state) and replayed; with a host-memory
 //     transport (ranks sharing a GPU) the exchange is a host node.
@@ -233,6 +239,20 @@ class Solver {
                       bool use_graph, std::vector<PassRec>* recs, std::vector<int64_t>* checks);
 
   void reduce_scalars(double* f64, int nf, uint64_t* u64, int nu, float* fmax, int nm);
+
+  // Insulated plate edges (Params::insulated).  An insulated side is a side
+  // with a neighbour whose data is the rank's own mirror image: the box of a
+  // pass grows toward it, its ghosts are refilled by every exchange
+  // (fill_insulated_ghosts), and an axis with one counts as decomposed.
+  bool insulated(int dir) const { return (P_.insulated >> dir) & 1; }
+  // The side has ghosts to keep: a neighbour rank, or this rank's own
+  // insulated plate edge (a rank without a neighbour on a side is at the
+  // plate edge there).
+  bool open_side(int dir) const { return blk_.nbr[size_t(dir)] >= 0 || insulated(dir); }
+  // Axis-level decisions, from global quantities only (every rank agrees).
+  bool ns_active() const { return cart_.px > 1 || (P_.insulated & 3) != 0; }
+  bool ew_active() const { return cart_.py > 1 || (P_.insulated & 12) != 0; }
+  int fill_sides() const;  // this rank's insulated plate edges (bits 1 << Dir)
 
   Params P_;
   std::shared_ptr<Transport> tr_;

@@ -65,6 +65,31 @@ const char* numerics_name(Numerics n) {
   return "?";
 }
 
+// Side letters in heat::Dir order (north, south, west, east).
+static const char kSideLetters[] = "nswe";
+
+bool parse_insulated(const std::string& s, uint8_t* out) {
+  uint8_t m = 0;
+  if (s == "all") {
+    m = kInsulatedAll;
+  } else {
+    for (char c : s) {
+      const char* at = c != '\0' ? std::strchr(kSideLetters, c) : nullptr;
+      if (at == nullptr) return false;
+      m |= uint8_t(1u << (at - kSideLetters));
+    }
+  }
+  *out = m;
+  return true;
+}
+
+std::string insulated_name(uint8_t mask) {
+  std::string s;
+  for (int d = 0; d < 4; ++d)
+    if ((mask >> d) & 1) s += kSideLetters[d];
+  return s;
+}
+
 Params params_from_c(const heat_params* p) {
   Params P;
   P.nx = p->nx;
@@ -91,6 +116,8 @@ Params params_from_c(const heat_params* p) {
   P.halo_passes = p->halo_passes;
   P.numerics = Numerics(p->numerics);
   P.phase_timing = p->phase_timing != 0;
+  HEAT_CHECK((p->insulated & ~int32_t(kInsulatedAll)) == 0, "insulated sides %d", p->insulated);
+  P.insulated = uint8_t(p->insulated);
   return P;
 }
 
@@ -346,7 +373,7 @@ int heat_solver_info(heat_solver* s, heat_block_info* o) {
     o->tb_depth = s->s->tb_depth();
     o->bytes_per_field = L.bytes();
     o->schedule = int32_t(s->s->schedule());
-    o->pad_ = 0;
+    o->insulated = int32_t(s->s->params().insulated);
   });
 }
 
@@ -554,6 +581,18 @@ int heat_op_residual(const float* a, const float* b, int64_t pitch, int64_t r0, 
   return guard([&] {
     heat::gpu::residual_box(a, b, pitch, heat::Box{r0, r1, c0, c1}, resid, S(stream));
   });
+}
+
+int heat_op_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
+                                  int depth, void* stream) {
+  return guard([&] {
+    heat::gpu::fill_insulated_ghosts(origin, pitch, lx, ly, sides, depth, S(stream));
+  });
+}
+
+int heat_cpu_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                                   int sides, int depth) {
+  return guard([&] { heat::cpu::fill_insulated_ghosts(origin, pitch, lx, ly, sides, depth); });
 }
 
 int heat_layout(int64_t lx, int64_t ly, int halo, int64_t* pitch, int64_t* rows, int* hx,

@@ -73,6 +73,36 @@ float step(const float* src, float* dst, const Geom& g, const Box& box, bool wan
   return want_resid ? m : 0.0f;
 }
 
+void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
+                           int depth) {
+  HEAT_CHECK((sides & ~15) == 0 && depth >= 1, "fill_insulated_ghosts: sides %d depth %d", sides,
+             depth);
+  const bool n = sides & (1 << North), s = sides & (1 << South), w = sides & (1 << West),
+             e = sides & (1 << East);
+  HEAT_CHECK(!(n || s) || lx > depth, "fill_insulated_ghosts: %lld rows, depth %d", (long long)lx,
+             depth);
+  HEAT_CHECK(!(w || e) || ly > depth, "fill_insulated_ghosts: %lld columns, depth %d",
+             (long long)ly, depth);
+  const int64_t d = depth;
+  // Every cell of the frame beyond an insulated side takes its per-axis
+  // reflection; the sources lie beyond no insulated side, so none is written.
+  auto mr = [&](int64_t r) { return (n && r < 0) ? -r : (s && r >= lx) ? 2 * (lx - 1) - r : r; };
+  auto mc = [&](int64_t c) { return (w && c < 0) ? -c : (e && c >= ly) ? 2 * (ly - 1) - c : c; };
+  for (int64_t r = -d; r < lx + d; ++r) {
+    const int64_t sr = mr(r);
+    float* dst = origin + r * pitch;
+    const float* src = origin + sr * pitch;
+    if (sr != r) {
+      for (int64_t c = -d; c < ly + d; ++c) dst[c] = src[mc(c)];
+    } else {
+      if (w)
+        for (int64_t c = -d; c < 0; ++c) dst[c] = src[-c];
+      if (e)
+        for (int64_t c = ly; c < ly + d; ++c) dst[c] = src[2 * (ly - 1) - c];
+    }
+  }
+}
+
 void copy_box(const float* src, int64_t src_pitch, float* dst, int64_t dst_pitch, const Box& box) {
   if (box.empty()) return;
 #pragma omp parallel for schedule(static) if (box.rows() > 64)

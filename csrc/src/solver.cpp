@@ -57,6 +57,14 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   HEAT_CHECK(tr_ != nullptr, "no transport");
   HEAT_CHECK(P_.nx >= 1 && P_.ny >= 1, "grid %lldx%lld", (long long)P_.nx, (long long)P_.ny);
   HEAT_CHECK(P_.check_interval >= 1, "check interval %d", P_.check_interval);
+  HEAT_CHECK((P_.insulated & ~kInsulatedAll) == 0, "insulated sides %d", int(P_.insulated));
+  // An insulated edge mirrors the row (column) next to it.
+  HEAT_CHECK((P_.insulated & 3) == 0 || P_.nx >= 2,
+             "an insulated north/south edge needs at least 2 rows, the plate has %lld",
+             (long long)P_.nx);
+  HEAT_CHECK((P_.insulated & 12) == 0 || P_.ny >= 2,
+             "an insulated west/east edge needs at least 2 columns, the plate has %lld",
+             (long long)P_.ny);
   cart_ = Cart(tr_->world(), P_.decomp, P_.px, P_.py, P_.nx, P_.ny);
   blk_ = make_block(cart_, tr_->rank(), P_.nx, P_.ny);
   if (on_gpu()) {
@@ -89,9 +97,18 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
     min_lx = std::min(min_lx, b.lx);
     min_ly = std::min(min_ly, b.ly);
   }
-  const int64_t min_ext = std::min(cart_.px > 1 ? min_lx : INT64_MAX, cart_.py > 1 ? min_ly : INT64_MAX);
+  // Along an axis with an insulated side a block must also hold the mirror
+  // sources, rows (columns) 1..H: one less than its extent.
+  const int64_t min_ext = halo_extent_limit(cart_, P_.nx, P_.ny, P_.insulated);
+  if (P_.insulated != 0 && min_ext < T_) {
+    // Not even one pass per exchange fits the thinnest block: a shallower pass.
+    HEAT_CHECK(min_ext >= 1, "a block of one row or column along an axis with an insulated side");
+    while (T_ > min_ext || (tb_kernel() && !gpu::tb_depth_supported(T_))) --T_;
+  }
   sched_ = P_.schedule == Schedule::Auto ? Schedule::Sync : P_.schedule;
-  if (!tb_kernel() || world == 1 || !P_.overlap)
+  // Insulated sides: the overlap schedules' bands and interiors assume that
+  // only neighbour sides have ghosts; they fall back to Sync.
+  if (!tb_kernel() || world == 1 || !P_.overlap || P_.insulated != 0)
     sched_ = Schedule::Sync;
   staged_ = on_gpu() && !tr_->device_memory() && world > 1;
   // Resident tiles for the workgroup-tile shapes (small per-rank blocks):
@@ -128,7 +145,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   // Ghost depth H = m*T: with the Sync schedule one exchange feeds m passes,
   // each computing the still-valid part of the ghost ring redundantly.
   int m = 1;
-  if (sched_ == Schedule::Sync && world > 1) {
+  if (sched_ == Schedule::Sync && (world > 1 || P_.insulated != 0)) {
     // m = 8 (H = 64 rows at K = 8, 96 at K = 12): larger m trades a few
     // percent of redundant ghost compute for fewer exchanges, whose
     // latency dominates on small blocks (profiles/halo_passes_r1.md).
@@ -147,7 +164,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
       if (res_shape) {
         const int rm = resident_halo_passes(cart_, P_.nx, P_.ny, T_, 8, [&](const Box& b) {
           return gpu::tb_resident_shape(b, T_);
-        });
+        }, P_.insulated);
         if (rm >= kResMinPasses) m = rm;
       }
     }
@@ -160,6 +177,10 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
              (long long)blk_.lx, H_);
   HEAT_CHECK(cart_.py == 1 || blk_.ly >= H_, "block of %lld cols is thinner than halo depth %d",
              (long long)blk_.ly, H_);
+  HEAT_CHECK((P_.insulated & 3) == 0 || blk_.lx > H_,
+             "block of %lld rows cannot mirror a halo of depth %d", (long long)blk_.lx, H_);
+  HEAT_CHECK((P_.insulated & 12) == 0 || blk_.ly > H_,
+             "block of %lld cols cannot mirror a halo of depth %d", (long long)blk_.ly, H_);
   // The boundary-first pipeline needs an interior box off H-deep bands.
   if (sched_ == Schedule::Pipeline &&
       !(min_lx > 2 * int64_t(H_) && round_down(min_ly - H_, 4) > round_up(H_, 4)))
@@ -177,7 +198,8 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   // cost ~21 %, and passes that drift apart lose the L2 sharing of the
   // synchronous launches (profiles/r5_chain.md).  Like resident tiles the
   // chained grid must own its device.
-  chain_ = on_gpu() && world == 1 && !resident_ && T_ == gpu::kTbDeepDepth && tb_kernel() &&
+  chain_ = on_gpu() && world == 1 && P_.insulated == 0 && !resident_ && T_ == gpu::kTbDeepDepth &&
+           tb_kernel() &&
            sched_ == Schedule::Sync && !staged_ && gpu::tb_tuning().variant < 0 &&
            env_int("HEAT_TB_CHAIN", 0) != 0;
   if (env_int("HEAT_TB_TRACE", 0) != 0)
@@ -612,6 +634,14 @@ void Solver::exchange(int buf, int k, hipStream_t st) {
   } else {
     for (int i = 0; i < nu; ++i) host_unpack(uk[i].buf, f, pitch, uk[i].box);
   }
+  // Insulated plate edges of this rank: their ghosts mirror the field, the
+  // ghost rows and columns the neighbours just filled included (the corners
+  // between an insulated side and a neighbour side).  In a world of one this
+  // is the whole exchange.
+  if (const int sides = fill_sides()) {
+    if (gpu) gpu::fill_insulated_ghosts(f, pitch, lx, ly, sides, k, st);
+    else cpu::fill_insulated_ghosts(f, pitch, lx, ly, sides, k);
+  }
   ++stat_exchanges_;
 }
 
@@ -658,16 +688,17 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
   const auto& nb = blk_.nbr;
   const int waves_target = gpu::tb_tuning().waves;
   // The box of this pass: the owned block grown by (er, ec) into the ghost
-  // ring on sides that have a neighbour (deep-halo passes).
-  const Box own{nb[North] >= 0 ? -er : 0, lx + (nb[South] >= 0 ? er : 0),
-                nb[West] >= 0 ? -ec : 0, ly + (nb[East] >= 0 ? ec : 0)};
+  // ring on sides that have a neighbour or are insulated (deep-halo passes).
+  const bool on = open_side(North), os = open_side(South), ow = open_side(West),
+             oe = open_side(East);
+  const Box own{on ? -er : 0, lx + (os ? er : 0), ow ? -ec : 0, ly + (oe ? ec : 0)};
 
   if (!tb_kernel()) {
     // k single steps over shrinking regions (deep halo), ping-ponging.
     for (int j = 0; j < k; ++j) {
       const int64_t e = k - 1 - j;
-      Box b{nb[North] >= 0 ? own.r0 - e : 0, own.r1 + (nb[South] >= 0 ? e : 0),
-            nb[West] >= 0 ? own.c0 - e : 0, own.c1 + (nb[East] >= 0 ? e : 0)};
+      Box b{on ? own.r0 - e : 0, own.r1 + (os ? e : 0), ow ? own.c0 - e : 0,
+            own.c1 + (oe ? e : 0)};
       const float* a = field_[cur_];
       float* d = field_[cur_ ^ 1];
       unsigned* rj = j == rl - 1 ? r : nullptr;
@@ -703,13 +734,27 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
   }
 }
 
+int Solver::fill_sides() const {
+  int sides = 0;
+  for (int d = 0; d < 4; ++d)
+    if (insulated(d) && blk_.nbr[size_t(d)] < 0) sides |= 1 << d;
+  return sides;
+}
+
 gpu::StencilGeom Solver::geom() const {
   gpu::StencilGeom g;
   g.pitch = L_.pitch;
-  g.gx0 = blk_.ox;
-  g.gy0 = blk_.oy;
-  g.nx = P_.nx;
-  g.ny = P_.ny;
+  // The plate the stencil kernels see: extended by the ghost depth beyond
+  // every insulated side, so that each real cell next to such a side is an
+  // interior cell (its missing neighbour: the mirror ghost) and the fixed
+  // ring lies on the outermost ghost cells, which no pass's box reaches.
+  // Everything else (initial condition, checksums, I/O) keeps the true plate.
+  const int64_t hn = insulated(North) ? H_ : 0, hs = insulated(South) ? H_ : 0;
+  const int64_t hw = insulated(West) ? H_ : 0, he = insulated(East) ? H_ : 0;
+  g.gx0 = blk_.ox + hn;
+  g.gy0 = blk_.oy + hw;
+  g.nx = P_.nx + hn + hs;
+  g.ny = P_.ny + hw + he;
   g.cx = P_.cx;
   g.cy = P_.cy;
   g.numerics = int(P_.numerics);
@@ -728,16 +773,16 @@ int Solver::resident_span(const std::vector<PassPlan>& plan, size_t i) const {
   if (tr_->world() > 1 && !resident_force_ && device_users(P_.device >= 0 ? P_.device : 0) > 1)
     return 0;
   const int k = plan[i].k;
-  const bool ns = cart_.px > 1, ew = cart_.py > 1;
+  const bool ns = ns_active(), ew = ew_active();
   // Ghost validity after the first pass's (possible) exchange, then the
   // bookkeeping of ensure_ghosts pass by pass: the span ends before a pass
   // that would need an exchange.
   int64_t gr = gr_, gc = gc_;
   if ((ns && gr < k) || (ew && gc < k)) gr = gc = H_;
-  const Box box{blk_.nbr[North] >= 0 ? -(ns ? gr - k : 0) : 0,
-                blk_.lx + (blk_.nbr[South] >= 0 ? (ns ? gr - k : 0) : 0),
-                blk_.nbr[West] >= 0 ? -(ew ? round_down(gc - k, 4) : 0) : 0,
-                blk_.ly + (blk_.nbr[East] >= 0 ? (ew ? round_down(gc - k, 4) : 0) : 0)};
+  const Box box{open_side(North) ? -(ns ? gr - k : 0) : 0,
+                blk_.lx + (open_side(South) ? (ns ? gr - k : 0) : 0),
+                open_side(West) ? -(ew ? round_down(gc - k, 4) : 0) : 0,
+                blk_.ly + (open_side(East) ? (ew ? round_down(gc - k, 4) : 0) : 0)};
   int n = 0, nchk = 0;
   for (size_t j = i; j < plan.size(); ++j) {
     if (plan[j].k != k) break;
@@ -767,9 +812,8 @@ void Solver::enqueue_resident(const std::vector<PassPlan>& plan, size_t i0, int 
   // ghost columns and rows the bookkeeping already treats as stale.
   const int64_t ex0 = stat_exchanges_;
   const auto ext = ensure_ghosts(k, s_comp_);
-  const auto& nb = blk_.nbr;
-  const Box box{nb[North] >= 0 ? -ext.first : 0, blk_.lx + (nb[South] >= 0 ? ext.first : 0),
-                nb[West] >= 0 ? -ext.second : 0, blk_.ly + (nb[East] >= 0 ? ext.second : 0)};
+  const Box box{open_side(North) ? -ext.first : 0, blk_.lx + (open_side(South) ? ext.first : 0),
+                open_side(West) ? -ext.second : 0, blk_.ly + (open_side(East) ? ext.second : 0)};
   for (int j = 1; j < n; ++j) (void)ensure_ghosts(k, s_comp_);
   HEAT_CHECK(stat_exchanges_ - ex0 <= 1, "resident span of %d passes needs an exchange", n);
   const int cur0 = cur_;
@@ -832,20 +876,20 @@ void Solver::enqueue_resident(const std::vector<PassPlan>& plan, size_t i0, int 
 void Solver::compute_cpu(int k, int rl, int64_t er, int64_t ec) {
   TraceRange trace("heat.compute");
   PhaseScope phase(this, kCompute, nullptr);
+  const gpu::StencilGeom sg = geom();  // the plate extended beyond insulated sides
   cpu::Geom g;
-  g.pitch = L_.pitch;
-  g.gx0 = blk_.ox;
-  g.gy0 = blk_.oy;
-  g.nx = P_.nx;
-  g.ny = P_.ny;
-  g.cx = P_.cx;
-  g.cy = P_.cy;
-  g.numerics = int(P_.numerics);
-  const auto& nb = blk_.nbr;
+  g.pitch = sg.pitch;
+  g.gx0 = sg.gx0;
+  g.gy0 = sg.gy0;
+  g.nx = sg.nx;
+  g.ny = sg.ny;
+  g.cx = sg.cx;
+  g.cy = sg.cy;
+  g.numerics = sg.numerics;
   for (int j = 0; j < k; ++j) {
     const int64_t e = k - 1 - j;
-    Box b{nb[North] >= 0 ? -(er + e) : 0, blk_.lx + (nb[South] >= 0 ? er + e : 0),
-          nb[West] >= 0 ? -(ec + e) : 0, blk_.ly + (nb[East] >= 0 ? ec + e : 0)};
+    Box b{open_side(North) ? -(er + e) : 0, blk_.lx + (open_side(South) ? er + e : 0),
+          open_side(West) ? -(ec + e) : 0, blk_.ly + (open_side(East) ? ec + e : 0)};
     const bool at = j == rl - 1;
     float r = cpu::step(field_[cur_], field_[cur_ ^ 1], g, b, at);
     if (at) cpu_resid_ = r;
@@ -864,8 +908,9 @@ std::pair<int64_t, int64_t> Solver::ensure_ghosts(int k, hipStream_t st) {
   // and short tail segments on 2 x 2 ranks).  The pass
   // then also updates the (valid - k) ghost rows/columns next to the block,
   // which become the valid ghosts of the next level.  Only axes that are
-  // decomposed count, so every rank makes the same decision.
-  const bool ns = cart_.px > 1, ew = cart_.py > 1;
+  // decomposed or have an insulated side count (global quantities), so every
+  // rank makes the same decision.
+  const bool ns = ns_active(), ew = ew_active();
   if ((ns && gr_ < k) || (ew && gc_ < k)) {
     exchange(cur_, H_, st);
     gr_ = gc_ = H_;
@@ -886,6 +931,8 @@ void Solver::enqueue_pass(int k, int rl) {
   const bool resid = rl > 0;
   // With world > 1 every rank of the (non-periodic) grid has a neighbour.
   const bool multi = tr_->world() > 1;
+  // Ghosts to keep valid: neighbours' halos, or a plate's insulated sides.
+  const bool ghosts = multi || P_.insulated != 0;
   PassRec rec;
   rec.step0 = step_;
   rec.k = k;
@@ -911,7 +958,7 @@ void Solver::enqueue_pass(int k, int rl) {
     // way (exchange || interior, then the bands).
     const bool comm_on_side = !(capturing_ && tr_->device_memory());
     side_interior_ = false;
-    if (!multi) {
+    if (!ghosts) {
       compute_gpu(k, rl, false, 0);
     } else if (sched_ == Schedule::Pipeline) {
       // Boundary-first: the H-deep ghosts of cur_ were exchanged by the
@@ -996,7 +1043,7 @@ void Solver::enqueue_pass(int k, int rl) {
     }
   } else {
     std::pair<int64_t, int64_t> ext{0, 0};
-    if (multi) ext = ensure_ghosts(k, nullptr);
+    if (ghosts) ext = ensure_ghosts(k, nullptr);
     compute_cpu(k, rl, ext.first, ext.second);
   }
   rec.cur1 = cur_;

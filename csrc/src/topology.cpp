@@ -125,31 +125,42 @@ Layout Layout::make(int64_t lx, int64_t ly, int halo) {
   return L;
 }
 
-Box span_box(const Cart& cart, const Block& b, int depth, int m) {
-  const int64_t gr = cart.px > 1 ? int64_t(m - 1) * depth : 0;
-  const int64_t gc = cart.py > 1 ? round_down(int64_t(m - 1) * depth, 4) : 0;
-  return Box{b.nbr[North] >= 0 ? -gr : 0, b.lx + (b.nbr[South] >= 0 ? gr : 0),
-             b.nbr[West] >= 0 ? -gc : 0, b.ly + (b.nbr[East] >= 0 ? gc : 0)};
+Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated) {
+  const bool ns = cart.px > 1 || (insulated & 3) != 0, ew = cart.py > 1 || (insulated & 12) != 0;
+  auto open = [&](int d) { return b.nbr[size_t(d)] >= 0 || ((insulated >> d) & 1) != 0; };
+  const int64_t gr = ns ? int64_t(m - 1) * depth : 0;
+  const int64_t gc = ew ? round_down(int64_t(m - 1) * depth, 4) : 0;
+  return Box{open(North) ? -gr : 0, b.lx + (open(South) ? gr : 0),
+             open(West) ? -gc : 0, b.ly + (open(East) ? gc : 0)};
+}
+
+int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated) {
+  const bool ins_x = (insulated & 3) != 0, ins_y = (insulated & 12) != 0;
+  int64_t ext = INT64_MAX;
+  for (int r = 0; r < cart.world; ++r) {
+    const Block b = make_block(cart, r, nx, ny);
+    if (cart.px > 1 || ins_x) ext = std::min(ext, b.lx - (ins_x ? 1 : 0));
+    if (cart.py > 1 || ins_y) ext = std::min(ext, b.ly - (ins_y ? 1 : 0));
+  }
+  return ext;
 }
 
 int resident_halo_passes(const Cart& cart, int64_t nx, int64_t ny, int depth, int mmax,
-                         const std::function<int(const Box&)>& shape) {
-  if (cart.world < 2 || depth < 1) return 0;
+                         const std::function<int(const Box&)>& shape, unsigned insulated) {
+  if ((cart.world < 2 && insulated == 0) || depth < 1) return 0;
   std::vector<Block> blocks;
   std::vector<int> own;
-  int64_t min_ext = INT64_MAX;
   for (int r = 0; r < cart.world; ++r) {
     blocks.push_back(make_block(cart, r, nx, ny));
     const Block& b = blocks.back();
     own.push_back(shape(Box{0, b.lx, 0, b.ly}));
     if (own.back() == 0) return 0;
-    if (cart.px > 1) min_ext = std::min(min_ext, b.lx);
-    if (cart.py > 1) min_ext = std::min(min_ext, b.ly);
   }
+  const int64_t min_ext = halo_extent_limit(cart, nx, ny, insulated);
   for (int m = int(std::min<int64_t>(mmax, min_ext / depth)); m >= 2; --m) {
     bool ok = true;
     for (size_t i = 0; i < blocks.size() && ok; ++i)
-      ok = shape(span_box(cart, blocks[i], depth, m)) == own[i];
+      ok = shape(span_box(cart, blocks[i], depth, m, insulated)) == own[i];
     if (ok) return m;
   }
   return 0;

@@ -20,7 +20,7 @@ import sys
 import torch
 
 from . import _native
-from .models.config import HeatConfig
+from .models.config import HeatConfig, parse_insulated
 from .models.heat2d import HeatSolver
 from .parallel import comm as pcomm
 from .utils import io as hio
@@ -59,6 +59,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--halo-passes", type=int, default=0)
     a("--numerics", choices=["fp32", "mpi"], default="fp32")
     a("--phase-timing", action="store_true")
+    a("--insulated", default="", metavar="SIDES",
+      help="insulated (zero-flux) plate edges: any of the letters nswe (n = row 0, w = column 0), "
+           "or all; the other edges keep their temperature")
     a("--transport", choices=["auto", "local", "rccl", "torch", "tcp", "loopback"], default="auto",
       help="loopback: --gpus ranks sharing a device (native binary)")
     a("--port", type=int, default=0, help="tcp transport rendezvous port (0: MASTER_PORT+1)")
@@ -80,7 +83,12 @@ def build_parser() -> argparse.ArgumentParser:
 
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    try:
+        parse_insulated(args.insulated)
+    except ValueError as e:
+        parser.error(str(e))
     if args.gpus > 0 or args.plan:
         # Single-process native modes: the `heat` binary owns the threads
         # and the planner; same flags, same output.
@@ -99,7 +107,7 @@ def main(argv=None) -> int:
                      px=args.px, py=args.py, use_graph=not args.no_graph,
                      overlap=not args.no_overlap, compat=compat, schedule=args.schedule,
                      halo_passes=args.halo_passes, numerics=args.numerics,
-                     phase_timing=args.phase_timing)
+                     phase_timing=args.phase_timing, insulated=args.insulated)
     info = pcomm.init_distributed("nccl" if backend == "hip" else "gloo")
     root = info.is_root
     out = sys.stdout
@@ -183,6 +191,7 @@ def main(argv=None) -> int:
                 transport=solver.transport, schedule=solver.info.schedule,
                 halo=solver.info.halo, t_exchange=acc["t_exchange"],
                 t_compute=acc["t_compute"], t_reduce=acc["t_reduce"],
+                insulated=solver.info.insulated,
                 native=_native.loaded_path()) + "\n")
         out.flush()
     solver.barrier()

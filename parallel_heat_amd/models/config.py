@@ -19,6 +19,22 @@ DECOMPS = {"auto": 0, "rows": 1, "1d": 1, "2d": 2}
 COMPATS = {"none": 0, "mpi": 1, "cuda": 2}
 SCHEDULES = {"auto": 0, "sync": 1, "overlap": 2, "pipeline": 3}
 NUMERICS = {"fp32": 0, "mpi": 1}
+SIDES = "nswe"  # north (row 0), south, west (column 0), east: heat::Dir order
+
+
+def parse_insulated(sides: str) -> str:
+    """Normalise an insulated-sides value ("", any subset of "nswe", or
+    "all") to its letters in n, s, w, e order; ValueError on anything else."""
+    if sides == "all":
+        return SIDES
+    if not isinstance(sides, str) or any(c not in SIDES for c in sides):
+        raise ValueError(f"insulated={sides!r}; expected 'all' or any of the letters {SIDES!r}")
+    return "".join(c for c in SIDES if c in sides)
+
+
+def insulated_mask(sides: str) -> int:
+    """Bit per side (1 north, 2 south, 4 west, 8 east), as Params::insulated."""
+    return sum(1 << SIDES.index(c) for c in parse_insulated(sides))
 
 
 @dataclass
@@ -48,6 +64,7 @@ class HeatConfig:
     halo_passes: int = 0          # sync: passes per halo exchange (ghost depth m*K); 0 = auto
     numerics: str = "fp32"        # fp32 (canonical FMA) | mpi (reference MPI double arithmetic)
     phase_timing: bool = False    # per-phase times (exchange/compute/reduce) in RunResult; eager
+    insulated: str = ""           # insulated (zero-flux) plate edges: any of "nswe", or "all"
 
     def replace(self, **kw) -> "HeatConfig":
         return dataclasses.replace(self, **kw)
@@ -64,6 +81,7 @@ class HeatConfig:
             raise ValueError("check_interval must be >= 1")
         if self.halo_passes < 0:
             raise ValueError("halo_passes must be >= 0")
+        parse_insulated(self.insulated)
 
     def total_steps(self) -> int:
         """Updates a full run performs (compat=mpi runs STEPS+1)."""
@@ -93,4 +111,5 @@ class HeatConfig:
         p.halo_passes = int(self.halo_passes)
         p.numerics = NUMERICS[self.numerics]
         p.phase_timing = int(bool(self.phase_timing))
+        p.insulated = insulated_mask(self.insulated)
         return p

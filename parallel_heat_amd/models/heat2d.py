@@ -21,7 +21,7 @@ import numpy as np
 
 from .. import _native
 from ..parallel import comm as pcomm
-from .config import HeatConfig
+from .config import SIDES, HeatConfig
 
 
 @dataclass
@@ -83,6 +83,7 @@ class BlockInfo:
     tb_depth: int
     bytes_per_field: int
     schedule: str
+    insulated: str = ""  # the run's insulated plate edges, letters of "nswe"
 
 
 class HeatSolver:
@@ -166,7 +167,8 @@ class HeatSolver:
         return BlockInfo(i.rank, i.world, i.px, i.py, i.cx, i.cy, i.ox, i.oy, i.lx, i.ly,
                          tuple(i.nbr), i.pitch, i.rows, i.hx, i.hy, i.halo, i.tb_depth,
                          i.bytes_per_field,
-                         {1: "sync", 2: "overlap", 3: "pipeline"}.get(i.schedule, "?"))
+                         {1: "sync", 2: "overlap", 3: "pipeline"}.get(i.schedule, "?"),
+                         "".join(c for k, c in enumerate(SIDES) if i.insulated >> k & 1))
 
     @property
     def step(self) -> int:

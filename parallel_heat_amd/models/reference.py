@@ -66,8 +66,39 @@ def init_grid(nx: int, ny: int, mode: str = "ref-wrap", seed: int = 0,
     raise ValueError(mode)
 
 
-def step_np(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
-    """One Jacobi step in float32; boundary ring unchanged."""
+_SIDES = "nswe"  # north = row 0, south = last row, west = column 0, east = last column
+
+
+def insulated_sides(insulated: str) -> str:
+    """"" | any subset of "nswe" | "all" -> the letters, validated."""
+    if insulated == "all":
+        return _SIDES
+    if any(c not in _SIDES for c in insulated):
+        raise ValueError(f"insulated={insulated!r}; expected 'all' or any of the letters {_SIDES!r}")
+    return insulated
+
+
+def _insulated_step(step, u, cx, cy, insulated):
+    """One step with insulated (zero-flux) sides, the second-order mirror
+    scheme: the grid is padded by one cell beyond every insulated side with
+    its reflection across the edge row / column (u[-1, j] := u[1, j], the edge
+    cell not repeated; a corner between two insulated sides takes both), the
+    Dirichlet step runs on the padded grid, whose ring it leaves fixed, and
+    the padding is cropped.  Edge cells of an insulated side are thereby
+    updated like interior cells; a corner shared with a Dirichlet side lies on
+    the padded grid's ring and stays fixed."""
+    ins = insulated_sides(insulated)
+    u = np.asarray(u, np.float32)
+    pad = ((int("n" in ins), int("s" in ins)), (int("w" in ins), int("e" in ins)))
+    v = step(np.pad(u, pad, mode="reflect"), cx, cy)
+    return np.ascontiguousarray(v[pad[0][0]:v.shape[0] - pad[0][1], pad[1][0]:v.shape[1] - pad[1][1]])
+
+
+def step_np(u: np.ndarray, cx: float = 0.1, cy: float = 0.1, insulated: str = "") -> np.ndarray:
+    """One Jacobi step in float32; boundary ring unchanged, except along the
+    `insulated` sides (letters of "nswe", or "all"; see _insulated_step)."""
+    if insulated:
+        return _insulated_step(step_np, u, cx, cy, insulated)
     u = np.asarray(u, np.float32)
     out = u.copy()
     if u.shape[0] < 3 or u.shape[1] < 3:
@@ -111,13 +142,18 @@ def fma32(a, b, c) -> np.ndarray:
         return s.astype(np.float32)
 
 
-def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
+def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
+                insulated: str = "") -> np.ndarray:
     """One step with the engine's default numerics, bit for bit: the
     expression of ``heat::stencil`` with the same operands in the same order,
         tx = fma(-2, c, s + n);  ty = fma(-2, c, e + w)
         u' = fma(cy, ty, fma(cx, tx, c))
     (n / s: rows above / below, w / e: columns left / right; cx and cy rounded
-    to float32 first, as HeatParams carries them); boundary ring unchanged."""
+    to float32 first, as HeatParams carries them); boundary ring unchanged,
+    except along the `insulated` sides (mirror scheme, _insulated_step: the
+    same expression, the missing neighbour being the cell's mirror image)."""
+    if insulated:
+        return _insulated_step(step_np_fma, u, cx, cy, insulated)
     u = np.asarray(u, np.float32)
     out = u.copy()
     if u.shape[0] < 3 or u.shape[1] < 3:
@@ -133,13 +169,16 @@ def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
     return out
 
 
-def step_np_mpi(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
+def step_np_mpi(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
+                insulated: str = "") -> np.ndarray:
     """One step with the reference MPI program's arithmetic
     (mpi/mpi_heat_improved_persistent_stat.c:168-174): the two neighbour sums
     in float32 (float + float in C), the rest in float64 because of the 2.0
     literal, evaluated left to right, rounded to float32 once.  NumPy float64
     ops are IEEE and never fused, so this is the exact oracle of
-    `numerics="mpi"`."""
+    `numerics="mpi"`.  `insulated`: as step_np."""
+    if insulated:
+        return _insulated_step(step_np_mpi, u, cx, cy, insulated)
     u = np.asarray(u, np.float32)
     out = u.copy()
     if u.shape[0] < 3 or u.shape[1] < 3:
@@ -153,8 +192,24 @@ def step_np_mpi(u: np.ndarray, cx: float = 0.1, cy: float = 0.1) -> np.ndarray:
     return out
 
 
-def step_torch(u: torch.Tensor, cx: float = 0.1, cy: float = 0.1) -> torch.Tensor:
-    """The same step as plain PyTorch fp32 ops (any device)."""
+def step_torch(u: torch.Tensor, cx: float = 0.1, cy: float = 0.1,
+               insulated: str = "") -> torch.Tensor:
+    """The same step as plain PyTorch fp32 ops (any device).  `insulated`: as
+    step_np."""
+    if insulated:
+        ins = insulated_sides(insulated)
+        p = u
+        if "n" in ins:
+            p = torch.cat([p[1:2], p], 0)
+        if "s" in ins:
+            p = torch.cat([p, p[-2:-1]], 0)
+        if "w" in ins:
+            p = torch.cat([p[:, 1:2], p], 1)
+        if "e" in ins:
+            p = torch.cat([p, p[:, -2:-1]], 1)
+        v = step_torch(p, cx, cy)
+        return v[int("n" in ins):v.shape[0] - int("s" in ins),
+                 int("w" in ins):v.shape[1] - int("e" in ins)].clone()
     out = u.clone()
     if u.shape[0] < 3 or u.shape[1] < 3:
         return out
@@ -176,16 +231,18 @@ def run_np(nx: int, ny: int, steps: int, cx: float = 0.1, cy: float = 0.1,
            converge: bool = False, check_interval: int = 20, eps: float = 1e-3,
            compat: str = "none", init: str = "ref-wrap", seed: int = 0,
            u0: Optional[np.ndarray] = None,
-           numerics: str = "fp32") -> Tuple[np.ndarray, int, int]:
+           numerics: str = "fp32", insulated: str = "") -> Tuple[np.ndarray, int, int]:
     """Run the model; returns (grid, steps_done, converged_at or -1).
     numerics: "fp32" (plain float32, a few ulps from the engine), "fma" (the
-    engine's default numerics, exact) or "mpi" (its numerics="mpi", exact)."""
+    engine's default numerics, exact) or "mpi" (its numerics="mpi", exact).
+    insulated: the plate's insulated (zero-flux) sides, letters of "nswe" or
+    "all"; the residual then covers their edge cells too."""
     step = {"fp32": step_np, "fma": step_np_fma, "mpi": step_np_mpi}[numerics]
     u = init_grid(nx, ny, init, seed) if u0 is None else np.array(u0, np.float32)
     total = steps + 1 if compat == "mpi" else steps
     checks = set(check_points(total, check_interval, compat)) if converge else set()
     for k in range(1, total + 1):
-        v = step(u, cx, cy)
+        v = step(u, cx, cy, insulated) if insulated else step(u, cx, cy)
         if k in checks:
             r = float(np.max(np.abs(v - u))) if v.size else 0.0
             ok = r <= eps if compat == "mpi" else r < np.float32(eps)

@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .. import _native
-from ..models.config import INIT_MODES
+from ..models.config import INIT_MODES, insulated_mask
 from ..parallel.topology import layout
 
 Box = Tuple[int, int, int, int]  # (r0, r1, c0, c1) in local coordinates
@@ -264,6 +264,26 @@ def unpack(buf: torch.Tensor, f: Field, box: Box) -> None:
         return
     _native.call("heat_op_unpack", ctypes.c_void_p(buf.data_ptr()), ctypes.c_void_p(f.ptr()),
                  f.pitch, r0, r1, c0, c1, ctypes.c_void_p(_stream()))
+
+
+def fill_insulated_ghosts(f: Field, sides: str, depth: int) -> None:
+    """Insulated (zero-flux) plate edges: fill the field's ghost frame, `depth`
+    cells deep, beyond every side in `sides` (letters of "nswe", or "all")
+    with the field's mirror image across that edge row / column (the edge cell
+    not repeated, both reflections beyond two insulated sides).  Only cells
+    beyond at least one of those sides are written.  One HIP launch on a GPU
+    field; the host twin the CPU backend uses on a CPU field."""
+    mask = insulated_mask(sides)
+    if depth < 1 or depth > f.halo:
+        raise ValueError(f"depth {depth} outside the field's ghost ring ({f.halo})")
+    if (mask & 3 and f.lx <= depth) or (mask & 12 and f.ly <= depth):
+        raise ValueError(f"a {f.lx} x {f.ly} field cannot mirror {depth} rows/columns")
+    if f.device.type == "cpu":
+        _native.call("heat_cpu_fill_insulated_ghosts", ctypes.c_void_p(f.ptr()), f.pitch, f.lx,
+                     f.ly, mask, depth)
+        return
+    _native.call("heat_op_fill_insulated_ghosts", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly,
+                 mask, depth, ctypes.c_void_p(_stream()))
 
 
 def residual(a: Field, b: Field, box: Optional[Box] = None,
