@@ -109,7 +109,12 @@ void naive_step(const float* src, float* dst, const StencilGeom& g, const Box& b
 // the register-streaming temporally blocked kernel.  Reads rows
 // [r0-depth, r1+depth) and columns [c0-round_up(depth,4), ...) of src, so the
 // ghost ring must be at least that deep and valid (halo exchanged).
-// Box column starts must be multiples of 4.  `waves_target` steers the row
+// Box column starts must be multiples of 4.  Writes: the boxes, and, since a
+// wave stores whole float4 lanes, possibly box rows x [c1, round_up(c1, 4))
+// with unspecified values (padding, or ghost columns the next exchange
+// refills); no other cell of dst (tests/test_gpu_edge_modes.py checks it on a
+// sentinel-filled field).  naive_step and lds_step write their box alone.
+// `waves_target` steers the row
 // chunking (parallelism vs. redundant halo work): > 0 absolute wave count,
 // 0 default rounds, < 0 that many whole rounds of resident waves.
 // `variant`: bits 0-1 pipeline (0: 3-row rings, skew 1; 1: 4-row rings,

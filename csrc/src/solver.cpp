@@ -172,11 +172,14 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   }
   H_ = m * T_;
   // A rank must own at least H rows/columns along every decomposed axis so
-  // that an H-deep halo comes from its direct neighbour only.
-  HEAT_CHECK(cart_.px == 1 || blk_.lx >= H_, "block of %lld rows is thinner than halo depth %d",
-             (long long)blk_.lx, H_);
-  HEAT_CHECK(cart_.py == 1 || blk_.ly >= H_, "block of %lld cols is thinner than halo depth %d",
-             (long long)blk_.ly, H_);
+  // that an H-deep halo comes from its direct neighbour only.  Judged on the
+  // thinnest block of any rank: with uneven blocks (23 rows on 3 ranks at
+  // depth 8: 8, 8, 7) every rank fails alike, instead of the thin rank alone
+  // while its peers go on to wait for it.
+  HEAT_CHECK(cart_.px == 1 || min_lx >= H_, "block of %lld rows is thinner than halo depth %d",
+             (long long)min_lx, H_);
+  HEAT_CHECK(cart_.py == 1 || min_ly >= H_, "block of %lld cols is thinner than halo depth %d",
+             (long long)min_ly, H_);
   HEAT_CHECK((P_.insulated & 3) == 0 || blk_.lx > H_,
              "block of %lld rows cannot mirror a halo of depth %d", (long long)blk_.lx, H_);
   HEAT_CHECK((P_.insulated & 12) == 0 || blk_.ly > H_,

@@ -81,6 +81,39 @@ def run_world(world, cfg_kwargs, steps, tmp_path, transport="torch", chunks=None
     return dict(np.load(out))
 
 
+def create_worker(rank, world, port, cfg_kwargs, out_dir):
+    """Only constructs the solver and writes what came of it ("ok" or the
+    error's text) into a file of its own: no rank ever waits for another, so
+    ranks that disagree show up as differing files, never as a hang."""
+    import torch.distributed as dist
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
+                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from parallel_heat_amd import HeatConfig, HeatSolver
+    from parallel_heat_amd.parallel.comm import DistInfo
+
+    try:
+        s = HeatSolver(HeatConfig(**cfg_kwargs), transport="torch",
+                       dist_info=DistInfo(rank, world, rank))
+        s.close()
+        text = "ok"
+    except Exception as e:  # noqa: BLE001 - the text is the result
+        text = f"{type(e).__name__}: {e}"
+    with open(os.path.join(out_dir, f"create_{rank}.txt"), "w") as f:
+        f.write(text)
+    dist.destroy_process_group()
+
+
+def run_create(world, cfg_kwargs, tmp_path):
+    """What constructing the solver gives on every rank of a gloo world."""
+    import torch.multiprocessing as mp
+
+    mp.spawn(create_worker, args=(world, free_port(), cfg_kwargs, str(tmp_path)), nprocs=world,
+             join=True)
+    return [(tmp_path / f"create_{r}.txt").read_text() for r in range(world)]
+
+
 def tune_worker(rank, world, port, cfg_kwargs, out_path, transport):
     """Runs parallel.tune.autotune on every rank; rank 0 saves the choice."""
     import json

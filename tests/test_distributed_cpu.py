@@ -58,6 +58,31 @@ def test_deep_halo_convergence_gloo(tmp_path):
     assert np.array_equal(res["grid"], ref)
 
 
+@pytest.mark.parametrize("world,kw,what", [
+    (3, dict(nx=23, ny=30, decomp="rows"), "7 rows"),      # blocks of 8, 8 and 7 rows
+    (3, dict(nx=30, ny=23, px=1, py=3), "7 cols"),         # blocks of 8, 8 and 7 columns
+])
+def test_block_thinner_than_halo_fails_on_every_rank(tmp_path, world, kw, what):
+    # Uneven blocks at depth 8: only the last rank's block is thinner than
+    # the halo.  Every rank must refuse (judged on the thinnest block), not
+    # that rank alone while its peers go on to wait for it.
+    from .dist_worker import run_create
+
+    cfg = dict(steps=0, init="random", seed=1, backend="cpu", tb_depth=8, **kw)
+    got = run_create(world, cfg, tmp_path)
+    assert len(got) == world
+    for text in got:
+        assert f"block of {what} is thinner than halo depth 8" in text, got
+
+
+def test_block_as_thick_as_halo_is_accepted_on_every_rank(tmp_path):
+    from .dist_worker import run_create
+
+    cfg = dict(nx=24, ny=30, steps=0, init="random", seed=1, backend="cpu", tb_depth=8,
+               decomp="rows")
+    assert run_create(3, cfg, tmp_path) == ["ok"] * 3
+
+
 def test_invariance_chunked_runs(tmp_path):
     kw = {**BASE, "tb_depth": 3}
     res = run_world(4, kw, 0, tmp_path, chunks=[5, 1, 17])

@@ -134,9 +134,9 @@ def _check(k, lv, g, dev, block=None, fill=0.0, res_level=0, boxes=None, numeric
     assert np.isfinite(got) and got == want, (got, want)
 
 
-def _plate(name, coef, steps=12, numerics="fma"):
-    g = ops.Geom(nx=LX, ny=LY, cx=coef[0], cy=coef[1])
-    return g, O.levels(name, LX, LY, coef[0], coef[1], steps, numerics)
+def _plate(name, coef, steps=12, numerics="fma", shape=(LX, LY)):
+    g = ops.Geom(nx=shape[0], ny=shape[1], cx=coef[0], cy=coef[1])
+    return g, O.levels(name, shape[0], shape[1], coef[0], coef[1], steps, numerics)
 
 
 # -- 1. every kernel family, anisotropic, [0, 100) data ------------------------
@@ -164,8 +164,8 @@ def test_inner_level_residual_anisotropic(gpu, k, rl, coef):
     _check(k, lv, g, gpu, res_level=rl)
 
 
-def _mfma_check(name, coef, dev):
-    g, lv = _plate(name, coef)
+def _mfma_check(name, coef, dev, shape=(LX, LY)):
+    g, lv = _plate(name, coef, shape=shape)
     a, b = _field(lv[0], dev, 4), _field(lv[0], dev, 4)
     r = torch.zeros(4, dtype=torch.int32, device=dev)
     K("mfma").run(a, b, g, resid=r)
