@@ -57,6 +57,8 @@ void usage() {
       "  --numerics fp32|mpi     update arithmetic (mpi = reference MPI double) [fp32]\n"
       "  --insulated SIDES       insulated (zero-flux) plate edges: any of n s w e (n = row 0,\n"
       "                          w = column 0), or all; the others keep their temperature []\n"
+      "  --periodic AXES         periodic (wrap-around) axes: x (north and south edges joined),\n"
+      "                          y (west and east joined) or xy []\n"
       "  --checkpoint PATH --checkpoint-every K   periodic binary checkpoints\n"
       "  --resume PATH           start from a binary checkpoint\n"
       "  --transport auto|local|tcp|rccl|loopback inter-rank transport  [auto]\n"
@@ -242,7 +244,7 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
           "\"mcells_per_s\": %.3f, \"s_per_1000_iters\": %.6f, \"converged\": %s, "
           "\"converged_at\": %lld, \"last_resid\": %.6g, \"passes\": %lld, \"exchanges\": %lld, "
           "\"transport\": \"%s\", \"schedule\": \"%s\", \"halo\": %d, \"t_exchange\": %.6f, "
-          "\"t_compute\": %.6f, \"t_reduce\": %.6f, \"insulated\": \"%s\"}\n",
+          "\"t_compute\": %.6f, \"t_reduce\": %.6f, \"insulated\": \"%s\", \"periodic\": \"%s\"}\n",
           (long long)P.nx, (long long)P.ny, (long long)total, (long long)acc.steps_done, world,
           P.backend == Backend::Hip ? "hip" : "cpu", c.px, c.py, S.tb_depth(), secs,
           secs > 0 ? cells / secs / 1e6 : 0.0,
@@ -250,7 +252,7 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
           acc.converged ? "true" : "false", (long long)acc.converged_at, double(acc.last_resid),
           (long long)acc.passes, (long long)acc.exchanges, S.transport().name(),
           schedule_name(S.schedule()), S.halo(), acc.t_exchange, acc.t_compute, acc.t_reduce,
-          insulated_name(P.insulated).c_str());
+          insulated_name(P.insulated).c_str(), periodic_name(P.periodic).c_str());
     }
     std::fflush(stdout);
   }
@@ -354,8 +356,21 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--periodic") {
+      const std::string s = need();
+      if (!parse_periodic(s, &P.periodic)) {
+        std::fprintf(stderr, "heat: --periodic %s: expected x, y or xy (x = north and south edges "
+                     "joined, y = west and east)\n", s.c_str());
+        return 2;
+      }
+    }
     else if (a == "--plan") plan = true;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 2; }
+  }
+  if (const char* axis = periodic_clash(P.insulated, P.periodic)) {
+    std::fprintf(stderr, "heat: axis %s is periodic (--periodic) and has an insulated side "
+                 "(--insulated): choose one\n", axis);
+    return 2;
   }
   if (o.naming == "mpi" && P.compat == Compat::None) P.compat = Compat::Mpi;
   if (o.naming == "cuda" && P.compat == Compat::None) P.compat = Compat::Cuda;
@@ -376,19 +391,23 @@ int main(int argc, char** argv) {
     auto shape = [&](const Box& b) { return resident_shape_static(b, depth); };
     // Insulated sides have ghosts too: a one-rank plate with one gets the
     // multi-rank halo depth, and along such an axis a block lends rows 1..H.
-    const bool ghosts = ranks > 1 || P.insulated != 0;
-    const int64_t ext = halo_extent_limit(cart, P.nx, P.ny, P.insulated);
+    // So have periodic axes, along which a block lends its last or first H rows.
+    const bool edge = P.insulated != 0 || P.periodic != 0;
+    const bool ghosts = ranks > 1 || edge;
+    const int64_t ext = halo_extent_limit(cart, P.nx, P.ny, P.insulated, P.periodic);
     int m = 1;
     if (ghosts) {
-      const int rm = resident_halo_passes(cart, P.nx, P.ny, depth, 8, shape, P.insulated);
+      const int rm = resident_halo_passes(cart, P.nx, P.ny, depth, 8, shape, P.insulated,
+                                          P.periodic);
       m = P.halo_passes > 0 ? P.halo_passes : rm >= kResMinPasses ? rm : 8;
-      if (P.insulated != 0) m = int(std::max<int64_t>(1, std::min<int64_t>(m, ext / depth)));
+      if (edge) m = int(std::max<int64_t>(1, std::min<int64_t>(m, ext / depth)));
     }
     bool resident = true;
     int res_rows = 0, res_waves = 0;
     for (int r = 0; r < ranks; ++r) {
-      const Block b = make_block(cart, r, P.nx, P.ny);
-      const int sh = shape(ghosts ? span_box(cart, b, depth, m, P.insulated) : Box{0, b.lx, 0, b.ly});
+      const Block b = make_block(cart, r, P.nx, P.ny, P.periodic);
+      const int sh = shape(ghosts ? span_box(cart, b, depth, m, P.insulated, P.periodic)
+                                  : Box{0, b.lx, 0, b.ly});
       resident = resident && sh != 0;
       if (r == 0) res_rows = sh >> 8, res_waves = sh & 255;
     }
@@ -398,7 +417,7 @@ int main(int argc, char** argv) {
       int64_t h = int64_t(depth) * m;
       if (cart.px > 1) h = std::min<int64_t>(h, b.lx);
       if (cart.py > 1) h = std::min<int64_t>(h, b.ly);
-      if (P.insulated != 0) h = std::min<int64_t>(h, ext);
+      if (edge) h = std::min<int64_t>(h, ext);
       const Layout L = Layout::make(b.lx, b.ly, int(std::max<int64_t>(1, h)));
       int64_t bytes = 2 * L.bytes();
       // Resident workgroup tiles (blocks under 64 strip-rows per SIMD on the

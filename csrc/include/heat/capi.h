@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define HEAT_ABI_VERSION 6
+#define HEAT_ABI_VERSION 7
 
 typedef struct heat_params {
   int64_t nx, ny;
@@ -40,6 +40,7 @@ typedef struct heat_params {
   int32_t numerics;    /* 0 fp32 (canonical FMA), 1 mpi (reference MPI double arithmetic) */
   int32_t phase_timing;/* 1: per-phase times in heat_run_stats (disables graphs) */
   int32_t insulated;   /* insulated (zero-flux) plate edges: 1 north, 2 south, 4 west, 8 east */
+  int32_t periodic;    /* periodic (wrap-around) axes: 1 x (north-south joined), 2 y (west-east) */
 } heat_params;
 
 /* Transport selection for heat_solver_create. */
@@ -79,6 +80,8 @@ typedef struct heat_block_info {
   int64_t bytes_per_field;
   int32_t schedule; /* effective heat::Schedule (1 sync, 2 overlap, 3 pipeline) */
   int32_t insulated; /* the run's insulated plate edges (heat_params.insulated) */
+  int32_t periodic;  /* the run's periodic axes (heat_params.periodic) */
+  int32_t pad_;
 } heat_block_info;
 
 typedef struct heat_checksum {
@@ -216,6 +219,14 @@ int heat_op_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int6
                                   int depth, void* stream);
 int heat_cpu_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
                                    int sides, int depth);
+/* The general fill of the `depth`-deep ghost frame: the mirror image beyond the
+   sides in `insulated_sides`, the field's opposite edge beyond both sides of the
+   axes in `periodic_axes` (1 x, 2 y); an axis cannot have both.  Device kernel
+   and host twin. */
+int heat_op_fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                             int insulated_sides, int periodic_axes, int depth, void* stream);
+int heat_cpu_fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                              int insulated_sides, int periodic_axes, int depth);
 int heat_layout(int64_t lx, int64_t ly, int halo, int64_t* pitch, int64_t* rows, int* hx,
                 int* hy);
 int heat_tb_supported(int depth);

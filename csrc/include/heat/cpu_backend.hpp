@@ -34,6 +34,10 @@ float step(const float* src, float* dst, const Geom& g, const Box& box, bool wan
 // into the `depth`-deep ghost frame beyond the insulated sides in `sides`.
 void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
                            int depth);
+// Host twin of gpu::fill_edge_ghosts: also wrap the field into the frame
+// beyond both sides of the axes in `periodic_axes` (1 x, 2 y).
+void fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int insulated_sides,
+                      int periodic_axes, int depth);
 
 void copy_box(const float* src, int64_t src_pitch, float* dst, int64_t dst_pitch, const Box& box);
 

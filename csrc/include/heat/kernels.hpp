@@ -26,7 +26,9 @@ namespace heat::gpu {
 // cell keeps its value.  Insulated plate edges (Params::insulated) reach the
 // kernels only through this geometry: the solver hands them a plate extended
 // by its ghost depth beyond every insulated side (Solver::geom), whose ghost
-// cells fill_insulated_ghosts keeps equal to the plate's mirror image.
+// cells fill_insulated_ghosts keeps equal to the plate's mirror image; a
+// periodic axis (Params::periodic) likewise, its ghost cells holding the
+// opposite edge of the plate (a neighbour rank's halo, or fill_edge_ghosts).
 struct StencilGeom {
   int64_t pitch = 0;
   int64_t gx0 = 0, gy0 = 0;
@@ -266,6 +268,17 @@ void unpack_box(const float* buf, float* origin, int64_t pitch, const Box& box, 
 // `sides` and a ghost ring at least `depth` deep.  Graph-capturable.
 void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
                            int depth, hipStream_t st);
+// The general fill, a mode per side: mirror beyond the sides in
+// `insulated_sides` as above, wrap beyond both sides of every axis in
+// `periodic_axes` (Params::periodic bits: an axis this rank spans alone),
+// (r < 0, c) := (r + lx, c), (r >= lx, c) := (r - lx, c), likewise for
+// columns; a frame cell's source is the per-axis composition of the maps, so a
+// corner between a wrapped axis and a mirrored or neighbour-filled side comes
+// out right in the same launch.  An axis cannot be wrapped and have a mirrored
+// side; a wrapped axis needs an extent >= depth.  fill_insulated_ghosts is
+// this with no periodic axis.
+void fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int insulated_sides,
+                      int periodic_axes, int depth, hipStream_t st);
 
 // Order-independent checksum of the owned block, accumulated on the device
 // into out (zeroed by the caller): hash (u64, wrapping sum of

@@ -100,12 +100,26 @@ struct Params {
   // 2 south, 4 west = column 0, 8 east); a clear bit is the fixed-temperature
   // (Dirichlet) edge of the reference.  See kInsulatedAll.
   uint8_t insulated = 0;
+  // Periodic (wrap-around) axes: bit 0 = x (rows: the north and south edges
+  // are joined), bit 1 = y (columns: west and east joined).  An axis cannot
+  // be periodic and have an insulated side.  See kPeriodicAll.
+  uint8_t periodic = 0;
 };
 
 constexpr uint8_t kInsulatedAll = 15;
+constexpr uint8_t kPeriodicX = 1, kPeriodicY = 2, kPeriodicAll = 3;
 // "" | any subset of "nswe" | "all" -> Params::insulated; false on a bad letter.
 bool parse_insulated(const std::string& s, uint8_t* out);
 std::string insulated_name(uint8_t mask);  // "" or the letters in n, s, w, e order
+// "" | "x" | "y" | "xy" (either order) -> Params::periodic; false on a bad letter.
+bool parse_periodic(const std::string& s, uint8_t* out);
+std::string periodic_name(uint8_t mask);  // "", "x", "y" or "xy"
+// The sides (bits 1 << heat::Dir) of the periodic axes in `periodic`.
+constexpr unsigned periodic_sides(unsigned periodic) {
+  return ((periodic & kPeriodicX) ? 3u : 0u) | ((periodic & kPeriodicY) ? 12u : 0u);
+}
+// The axis ("x" / "y") that is periodic and also has an insulated side; nullptr if none.
+const char* periodic_clash(unsigned insulated, unsigned periodic);
 
 const char* init_mode_name(InitMode m);
 const char* kernel_name(KernelKind k);

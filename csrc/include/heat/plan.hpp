@@ -16,8 +16,10 @@ namespace heat {
 // to 4) on every side with a neighbour along a decomposed axis, as
 // Solver::resident_span tracks ghost validity.  `insulated`
 // (Params::insulated): an insulated plate edge counts as a neighbour, and an
-// axis with one as decomposed.
-Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated = 0);
+// axis with one as decomposed.  `periodic` (Params::periodic): both sides of a
+// periodic axis count as neighbours, and the axis as decomposed.
+Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated = 0,
+             unsigned periodic = 0);
 
 // A resident tile plan's shape as one int: rows per wave << 8 | waves per
 // workgroup (0: the box has no one-round resident plan).
@@ -43,13 +45,17 @@ constexpr int kResMinPasses = 4;
 //   8192^2 on 2 x 2: m = 5 (4144^2, 20 x 16) 4.73, m = 8 (4180^2, split
 //     pipelines) 3.79.
 int resident_halo_passes(const Cart& cart, int64_t nx, int64_t ny, int depth, int mmax,
-                         const std::function<int(const Box&)>& shape, unsigned insulated = 0);
+                         const std::function<int(const Box&)>& shape, unsigned insulated = 0,
+                         unsigned periodic = 0);
 
 // Rows (columns) a rank can lend to an H-deep halo along each axis: the
 // smallest block extent of any rank along a decomposed axis, one less along
-// an axis with an insulated side (its ghosts mirror rows 1..H); INT64_MAX
-// along an axis with neither.  The ghost depth is at most the smaller one.
-int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated);
+// an axis with an insulated side (its ghosts mirror rows 1..H); the smallest
+// block extent itself along a periodic axis (wrap sources are the last or
+// first H rows of a block); INT64_MAX along an axis with none of these.  The
+// ghost depth is at most the smaller one.
+int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated,
+                          unsigned periodic = 0);
 
 // Host-side resident plan of a box at `depth` on an MI355X (`cus` CUs): the
 // tile planner's shapes and choice (tb_resident.hip plan_res: the lowest

@@ -24,6 +24,9 @@
 //     fill_insulated_ghosts launch after the unpack; the whole exchange in a
 //     world of one), the pass boxes grow toward it, and the stencil kernels
 //     get a plate extended by H beyond it (geom()), so none of them changes.
+//   * Periodic axes (Params::periodic) are the same with another source: the
+//     neighbour of an end rank is the rank at the other end of the axis, or,
+//     with one rank along it, the rank's own opposite edge (fill_edge_ghosts).
 //   * Segments between convergence checks are captured once into a hipGraph
 //     per (length, parity, ghost state) and replayed; with a host-memory
 //     transport (ranks sharing a GPU) the exchange is a host node.
@@ -245,13 +248,28 @@ class Solver {
   // pass grows toward it, its ghosts are refilled by every exchange
   // (fill_insulated_ghosts), and an axis with one counts as decomposed.
   bool insulated(int dir) const { return (P_.insulated >> dir) & 1; }
+  // Periodic axes (Params::periodic): both sides of a periodic axis are
+  // non-fixed too.  Their neighbour is the rank at the other end of the axis
+  // (Cart::neighbors wraps: an ordinary neighbour side of exchange()), or,
+  // with one rank along the axis, this rank's own opposite edge.
+  bool periodic(int dir) const { return (periodic_sides(P_.periodic) >> dir) & 1; }
+  bool edge_ghosts() const { return P_.insulated != 0 || P_.periodic != 0; }
   // The side has ghosts to keep: a neighbour rank, or this rank's own
-  // insulated plate edge (a rank without a neighbour on a side is at the
-  // plate edge there).
-  bool open_side(int dir) const { return blk_.nbr[size_t(dir)] >= 0 || insulated(dir); }
+  // insulated or periodic plate edge (a rank without a neighbour on a side is
+  // at the plate edge there).
+  bool open_side(int dir) const {
+    return blk_.nbr[size_t(dir)] >= 0 || insulated(dir) || periodic(dir);
+  }
   // Axis-level decisions, from global quantities only (every rank agrees).
-  bool ns_active() const { return cart_.px > 1 || (P_.insulated & 3) != 0; }
-  bool ew_active() const { return cart_.py > 1 || (P_.insulated & 12) != 0; }
+  bool ns_active() const {
+    return cart_.px > 1 || (P_.insulated & 3) != 0 || (P_.periodic & kPeriodicX) != 0;
+  }
+  bool ew_active() const {
+    return cart_.py > 1 || (P_.insulated & 12) != 0 || (P_.periodic & kPeriodicY) != 0;
+  }
+  // This rank's locally wrapped axes (Params::periodic bits): periodic, and
+  // spanned by this rank alone.
+  int fill_axes() const;
   int fill_sides() const;  // this rank's insulated plate edges (bits 1 << Dir)
 
   Params P_;

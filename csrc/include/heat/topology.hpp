@@ -43,8 +43,14 @@ struct Cart {
   // Row-major rank order like MPI_Cart_create with reorder=0: rank = cx*py + cy.
   std::array<int, 2> coords(int rank) const { return {rank / py, rank % py}; }
   int rank_of(int cx, int cy) const;  // kNoNeighbor if outside (non-periodic)
-  std::array<int, 4> neighbors(int rank) const;
-  std::array<int, 4> diagonal_neighbors(int rank) const;
+  // `periodic` (Params::periodic, bit 0 = x, bit 1 = y): along a periodic axis
+  // with more than one rank the coordinate wraps, so the neighbour of an end
+  // rank is the rank at the other end (diagonals wrap on that axis too).
+  // With one rank along the axis the neighbour stays kNoNeighbor: the rank
+  // fills its own ghosts.
+  int rank_of(int cx, int cy, unsigned periodic) const;
+  std::array<int, 4> neighbors(int rank, unsigned periodic = 0) const;
+  std::array<int, 4> diagonal_neighbors(int rank, unsigned periodic = 0) const;
 };
 
 // 1-D block partition with remainder distribution: the first (n % p) parts
@@ -64,7 +70,7 @@ struct Block {
   std::array<int, 4> diag{kNoNeighbor, kNoNeighbor, kNoNeighbor, kNoNeighbor};
 };
 
-Block make_block(const Cart& cart, int rank, int64_t nx, int64_t ny);
+Block make_block(const Cart& cart, int rank, int64_t nx, int64_t ny, unsigned periodic = 0);
 
 // Memory layout of one local field: owned block plus a ghost ring of
 // `hx` rows and `hy` columns on every side, with the row pitch padded to a

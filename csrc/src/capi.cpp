@@ -90,6 +90,26 @@ std::string insulated_name(uint8_t mask) {
   return s;
 }
 
+bool parse_periodic(const std::string& s, uint8_t* out) {
+  uint8_t m = 0;
+  for (char c : s) {
+    if (c != 'x' && c != 'y') return false;
+    m |= c == 'x' ? kPeriodicX : kPeriodicY;
+  }
+  *out = m;
+  return true;
+}
+
+std::string periodic_name(uint8_t mask) {
+  return std::string((mask & kPeriodicX) ? "x" : "") + ((mask & kPeriodicY) ? "y" : "");
+}
+
+const char* periodic_clash(unsigned insulated, unsigned periodic) {
+  if ((periodic & kPeriodicX) && (insulated & 3)) return "x";
+  if ((periodic & kPeriodicY) && (insulated & 12)) return "y";
+  return nullptr;
+}
+
 Params params_from_c(const heat_params* p) {
   Params P;
   P.nx = p->nx;
@@ -118,6 +138,8 @@ Params params_from_c(const heat_params* p) {
   P.phase_timing = p->phase_timing != 0;
   HEAT_CHECK((p->insulated & ~int32_t(kInsulatedAll)) == 0, "insulated sides %d", p->insulated);
   P.insulated = uint8_t(p->insulated);
+  HEAT_CHECK((p->periodic & ~int32_t(kPeriodicAll)) == 0, "periodic axes %d", p->periodic);
+  P.periodic = uint8_t(p->periodic);
   return P;
 }
 
@@ -374,6 +396,8 @@ int heat_solver_info(heat_solver* s, heat_block_info* o) {
     o->bytes_per_field = L.bytes();
     o->schedule = int32_t(s->s->schedule());
     o->insulated = int32_t(s->s->params().insulated);
+    o->periodic = int32_t(s->s->params().periodic);
+    o->pad_ = 0;
   });
 }
 
@@ -593,6 +617,21 @@ int heat_op_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int6
 int heat_cpu_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
                                    int sides, int depth) {
   return guard([&] { heat::cpu::fill_insulated_ghosts(origin, pitch, lx, ly, sides, depth); });
+}
+
+int heat_op_fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                             int insulated_sides, int periodic_axes, int depth, void* stream) {
+  return guard([&] {
+    heat::gpu::fill_edge_ghosts(origin, pitch, lx, ly, insulated_sides, periodic_axes, depth,
+                                S(stream));
+  });
+}
+
+int heat_cpu_fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                              int insulated_sides, int periodic_axes, int depth) {
+  return guard([&] {
+    heat::cpu::fill_edge_ghosts(origin, pitch, lx, ly, insulated_sides, periodic_axes, depth);
+  });
 }
 
 int heat_layout(int64_t lx, int64_t ly, int halo, int64_t* pitch, int64_t* rows, int* hx,

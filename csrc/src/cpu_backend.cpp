@@ -73,21 +73,37 @@ float step(const float* src, float* dst, const Geom& g, const Box& box, bool wan
   return want_resid ? m : 0.0f;
 }
 
-void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
-                           int depth) {
-  HEAT_CHECK((sides & ~15) == 0 && depth >= 1, "fill_insulated_ghosts: sides %d depth %d", sides,
-             depth);
-  const bool n = sides & (1 << North), s = sides & (1 << South), w = sides & (1 << West),
-             e = sides & (1 << East);
+void fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int insulated_sides,
+                      int periodic_axes, int depth) {
+  HEAT_CHECK((insulated_sides & ~15) == 0 && (periodic_axes & ~3) == 0 && depth >= 1,
+             "fill_edge_ghosts: sides %d axes %d depth %d", insulated_sides, periodic_axes, depth);
+  const bool wx = periodic_axes & kPeriodicX, wy = periodic_axes & kPeriodicY;
+  HEAT_CHECK(!(wx && (insulated_sides & 3)), "fill_edge_ghosts: axis x both wrapped and mirrored");
+  HEAT_CHECK(!(wy && (insulated_sides & 12)), "fill_edge_ghosts: axis y both wrapped and mirrored");
+  const bool n = insulated_sides & (1 << North), s = insulated_sides & (1 << South),
+             w = insulated_sides & (1 << West), e = insulated_sides & (1 << East);
   HEAT_CHECK(!(n || s) || lx > depth, "fill_insulated_ghosts: %lld rows, depth %d", (long long)lx,
              depth);
   HEAT_CHECK(!(w || e) || ly > depth, "fill_insulated_ghosts: %lld columns, depth %d",
              (long long)ly, depth);
+  HEAT_CHECK(!wx || lx >= depth, "fill_edge_ghosts: %lld rows wrapped, depth %d", (long long)lx,
+             depth);
+  HEAT_CHECK(!wy || ly >= depth, "fill_edge_ghosts: %lld columns wrapped, depth %d", (long long)ly,
+             depth);
   const int64_t d = depth;
-  // Every cell of the frame beyond an insulated side takes its per-axis
-  // reflection; the sources lie beyond no insulated side, so none is written.
-  auto mr = [&](int64_t r) { return (n && r < 0) ? -r : (s && r >= lx) ? 2 * (lx - 1) - r : r; };
-  auto mc = [&](int64_t c) { return (w && c < 0) ? -c : (e && c >= ly) ? 2 * (ly - 1) - c : c; };
+  // Every cell of the frame beyond a filled side takes its per-axis source
+  // (reflected beyond an insulated side, shifted by the extent along a
+  // periodic axis); the sources lie beyond no filled side, so none is written.
+  auto mr = [&](int64_t r) {
+    if (r < 0) return n ? -r : wx ? r + lx : r;
+    if (r >= lx) return s ? 2 * (lx - 1) - r : wx ? r - lx : r;
+    return r;
+  };
+  auto mc = [&](int64_t c) {
+    if (c < 0) return w ? -c : wy ? c + ly : c;
+    if (c >= ly) return e ? 2 * (ly - 1) - c : wy ? c - ly : c;
+    return c;
+  };
   for (int64_t r = -d; r < lx + d; ++r) {
     const int64_t sr = mr(r);
     float* dst = origin + r * pitch;
@@ -95,12 +111,19 @@ void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly,
     if (sr != r) {
       for (int64_t c = -d; c < ly + d; ++c) dst[c] = src[mc(c)];
     } else {
-      if (w)
-        for (int64_t c = -d; c < 0; ++c) dst[c] = src[-c];
-      if (e)
-        for (int64_t c = ly; c < ly + d; ++c) dst[c] = src[2 * (ly - 1) - c];
+      if (w || wy)
+        for (int64_t c = -d; c < 0; ++c) dst[c] = src[mc(c)];
+      if (e || wy)
+        for (int64_t c = ly; c < ly + d; ++c) dst[c] = src[mc(c)];
     }
   }
+}
+
+void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
+                           int depth) {
+  HEAT_CHECK((sides & ~15) == 0 && depth >= 1, "fill_insulated_ghosts: sides %d depth %d", sides,
+             depth);
+  fill_edge_ghosts(origin, pitch, lx, ly, sides, 0, depth);
 }
 
 void copy_box(const float* src, int64_t src_pitch, float* dst, int64_t dst_pitch, const Box& box) {

@@ -65,8 +65,11 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   HEAT_CHECK((P_.insulated & 12) == 0 || P_.ny >= 2,
              "an insulated west/east edge needs at least 2 columns, the plate has %lld",
              (long long)P_.ny);
+  HEAT_CHECK((P_.periodic & ~kPeriodicAll) == 0, "periodic axes %d", int(P_.periodic));
+  if (const char* axis = periodic_clash(P_.insulated, P_.periodic))
+    HEAT_CHECK(false, "axis %s is periodic and has an insulated side: choose one", axis);
   cart_ = Cart(tr_->world(), P_.decomp, P_.px, P_.py, P_.nx, P_.ny);
-  blk_ = make_block(cart_, tr_->rank(), P_.nx, P_.ny);
+  blk_ = make_block(cart_, tr_->rank(), P_.nx, P_.ny, P_.periodic);
   if (on_gpu()) {
     // The TB kernel evaluates the canonical fp32 expression only.
     if (P_.numerics != Numerics::Fp32) {
@@ -98,17 +101,19 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
     min_ly = std::min(min_ly, b.ly);
   }
   // Along an axis with an insulated side a block must also hold the mirror
-  // sources, rows (columns) 1..H: one less than its extent.
-  const int64_t min_ext = halo_extent_limit(cart_, P_.nx, P_.ny, P_.insulated);
-  if (P_.insulated != 0 && min_ext < T_) {
+  // sources, rows (columns) 1..H: one less than its extent.  Along a periodic
+  // axis the wrap sources are a block's last or first H rows: its extent.
+  const int64_t min_ext = halo_extent_limit(cart_, P_.nx, P_.ny, P_.insulated, P_.periodic);
+  if (edge_ghosts() && min_ext < T_) {
     // Not even one pass per exchange fits the thinnest block: a shallower pass.
     HEAT_CHECK(min_ext >= 1, "a block of one row or column along an axis with an insulated side");
     while (T_ > min_ext || (tb_kernel() && !gpu::tb_depth_supported(T_))) --T_;
   }
   sched_ = P_.schedule == Schedule::Auto ? Schedule::Sync : P_.schedule;
   // Insulated sides: the overlap schedules' bands and interiors assume that
-  // only neighbour sides have ghosts; they fall back to Sync.
-  if (!tb_kernel() || world == 1 || !P_.overlap || P_.insulated != 0)
+  // only neighbour sides have ghosts; they fall back to Sync.  So do periodic
+  // axes, whose end ranks have ghosts beyond the plate.
+  if (!tb_kernel() || world == 1 || !P_.overlap || edge_ghosts())
     sched_ = Schedule::Sync;
   staged_ = on_gpu() && !tr_->device_memory() && world > 1;
   // Resident tiles for the workgroup-tile shapes (small per-rank blocks):
@@ -145,7 +150,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   // Ghost depth H = m*T: with the Sync schedule one exchange feeds m passes,
   // each computing the still-valid part of the ghost ring redundantly.
   int m = 1;
-  if (sched_ == Schedule::Sync && (world > 1 || P_.insulated != 0)) {
+  if (sched_ == Schedule::Sync && (world > 1 || edge_ghosts())) {
     // m = 8 (H = 64 rows at K = 8, 96 at K = 12): larger m trades a few
     // percent of redundant ghost compute for fewer exchanges, whose
     // latency dominates on small blocks (profiles/halo_passes_r1.md).
@@ -164,7 +169,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
       if (res_shape) {
         const int rm = resident_halo_passes(cart_, P_.nx, P_.ny, T_, 8, [&](const Box& b) {
           return gpu::tb_resident_shape(b, T_);
-        }, P_.insulated);
+        }, P_.insulated, P_.periodic);
         if (rm >= kResMinPasses) m = rm;
       }
     }
@@ -184,6 +189,10 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
              "block of %lld rows cannot mirror a halo of depth %d", (long long)blk_.lx, H_);
   HEAT_CHECK((P_.insulated & 12) == 0 || blk_.ly > H_,
              "block of %lld cols cannot mirror a halo of depth %d", (long long)blk_.ly, H_);
+  HEAT_CHECK((P_.periodic & kPeriodicX) == 0 || min_lx >= H_,
+             "block of %lld rows cannot wrap a halo of depth %d", (long long)min_lx, H_);
+  HEAT_CHECK((P_.periodic & kPeriodicY) == 0 || min_ly >= H_,
+             "block of %lld cols cannot wrap a halo of depth %d", (long long)min_ly, H_);
   // The boundary-first pipeline needs an interior box off H-deep bands.
   if (sched_ == Schedule::Pipeline &&
       !(min_lx > 2 * int64_t(H_) && round_down(min_ly - H_, 4) > round_up(H_, 4)))
@@ -201,7 +210,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   // cost ~21 %, and passes that drift apart lose the L2 sharing of the
   // synchronous launches (profiles/r5_chain.md).  Like resident tiles the
   // chained grid must own its device.
-  chain_ = on_gpu() && world == 1 && P_.insulated == 0 && !resident_ && T_ == gpu::kTbDeepDepth &&
+  chain_ = on_gpu() && world == 1 && !edge_ghosts() && !resident_ && T_ == gpu::kTbDeepDepth &&
            tb_kernel() &&
            sched_ == Schedule::Sync && !staged_ && gpu::tb_tuning().variant < 0 &&
            env_int("HEAT_TB_CHAIN", 0) != 0;
@@ -602,29 +611,53 @@ void Solver::exchange(int buf, int k, hipStream_t st) {
   gpu::BoxCopy pk[6], uk[6];
   int np = 0, nu = 0;
   const size_t ew_bytes = size_t(lx) * size_t(k) * 4, c_bytes = size_t(k) * size_t(k) * 4;
-  if (nb[West] >= 0) {
-    pk[np++] = {sw, ew_[0]};
-    uk[nu++] = {rw, ew_[2]};
-    msgs.push_back(Msg{nb[West], ew_[0], ew_bytes, ew_[2], ew_bytes});
-  }
-  if (nb[East] >= 0) {
-    pk[np++] = {se, ew_[1]};
-    uk[nu++] = {re, ew_[3]};
-    msgs.push_back(Msg{nb[East], ew_[1], ew_bytes, ew_[3], ew_bytes});
+  // Every transport pairs the messages of a rank pair in FIFO order, and a Msg
+  // couples one send with one receive from the same peer.  Along a periodic
+  // axis with two ranks both sides of a block have the same peer (on a 2 x 2
+  // periodic grid all four diagonals): the j-th send to a peer must then meet
+  // the receive that wants it.  The peer lists its receives from us by the
+  // direction its data left us, in the order we list our sends, so: sends to
+  // a peer in direction order, each coupled with the receive of the ghost
+  // opposite to the j-th direction from the end of that peer's list.  With
+  // distinct peers that is the ghost on the send's own side, as ever; sizes
+  // are equal within a peer's list either way.
+  auto recv_slot = [](const int* peers, int n, int d) {
+    // Directions toward peers[d], ascending; position j of d; the j-th of the
+    // opposites (n - 1 - .) ascending, i.e. the directions descending.
+    int same[4], cnt = 0, j = 0;
+    for (int e = 0; e < n; ++e)
+      if (peers[e] == peers[d]) {
+        if (e == d) j = cnt;
+        same[cnt++] = e;
+      }
+    return same[cnt - 1 - j];
+  };
+  const int we[2] = {nb[West], nb[East]}, ns[2] = {nb[North], nb[South]};
+  const Box ew_send[2] = {sw, se}, ew_recv[2] = {rw, re};
+  for (int d = 0; d < 2; ++d) {
+    if (we[d] < 0) continue;
+    const int g = recv_slot(we, 2, d);
+    pk[np++] = {ew_send[d], ew_[d]};
+    uk[nu++] = {ew_recv[g], ew_[2 + g]};
+    msgs.push_back(Msg{we[d], ew_[d], ew_bytes, ew_[2 + g], ew_bytes});
   }
   for (int d = 0; d < 4; ++d) {
     if (blk_.diag[d] < 0) continue;
+    const int g = recv_slot(blk_.diag.data(), 4, d);
     pk[np++] = {csend[d], cn_[d]};
-    uk[nu++] = {crecv[d], cn_[4 + d]};
-    msgs.push_back(Msg{blk_.diag[d], cn_[d], c_bytes, cn_[4 + d], c_bytes});
+    uk[nu++] = {crecv[g], cn_[4 + g]};
+    msgs.push_back(Msg{blk_.diag[d], cn_[d], c_bytes, cn_[4 + g], c_bytes});
   }
-  if (nb[North] >= 0 || nb[South] >= 0) {
+  {
     const size_t bytes = size_t(k) * size_t(pitch) * 4;
     const int64_t hy = L_.hy;
-    if (nb[North] >= 0)
-      msgs.push_back(Msg{nb[North], f - hy, bytes, f - k * pitch - hy, bytes});
-    if (nb[South] >= 0)
-      msgs.push_back(Msg{nb[South], f + (lx - k) * pitch - hy, bytes, f + lx * pitch - hy, bytes});
+    float* const send[2] = {f - hy, f + (lx - k) * pitch - hy};
+    float* const recv[2] = {f - k * pitch - hy, f + lx * pitch - hy};
+    for (int d = 0; d < 2; ++d) {
+      if (ns[d] < 0) continue;
+      const int g = recv_slot(ns, 2, d);
+      msgs.push_back(Msg{ns[d], send[d], bytes, recv[g], bytes});
+    }
   }
   if (gpu) {
     gpu::copy_boxes(f, pitch, pk, np, true, st);
@@ -640,10 +673,12 @@ void Solver::exchange(int buf, int k, hipStream_t st) {
   // Insulated plate edges of this rank: their ghosts mirror the field, the
   // ghost rows and columns the neighbours just filled included (the corners
   // between an insulated side and a neighbour side).  In a world of one this
-  // is the whole exchange.
-  if (const int sides = fill_sides()) {
-    if (gpu) gpu::fill_insulated_ghosts(f, pitch, lx, ly, sides, k, st);
-    else cpu::fill_insulated_ghosts(f, pitch, lx, ly, sides, k);
+  // is the whole exchange.  Likewise the periodic axes this rank spans alone,
+  // whose ghosts take the field's opposite edge.
+  const int sides = fill_sides(), axes = fill_axes();
+  if (sides != 0 || axes != 0) {
+    if (gpu) gpu::fill_edge_ghosts(f, pitch, lx, ly, sides, axes, k, st);
+    else cpu::fill_edge_ghosts(f, pitch, lx, ly, sides, axes, k);
   }
   ++stat_exchanges_;
 }
@@ -744,16 +779,24 @@ int Solver::fill_sides() const {
   return sides;
 }
 
+int Solver::fill_axes() const {
+  int axes = 0;
+  if ((P_.periodic & kPeriodicX) && cart_.px == 1) axes |= kPeriodicX;
+  if ((P_.periodic & kPeriodicY) && cart_.py == 1) axes |= kPeriodicY;
+  return axes;
+}
+
 gpu::StencilGeom Solver::geom() const {
   gpu::StencilGeom g;
   g.pitch = L_.pitch;
   // The plate the stencil kernels see: extended by the ghost depth beyond
-  // every insulated side, so that each real cell next to such a side is an
-  // interior cell (its missing neighbour: the mirror ghost) and the fixed
+  // every insulated side and along every periodic axis, so that each real
+  // cell next to such a side is an interior cell (its missing neighbour: the
+  // mirror ghost, or the ghost holding the opposite edge) and the fixed
   // ring lies on the outermost ghost cells, which no pass's box reaches.
   // Everything else (initial condition, checksums, I/O) keeps the true plate.
-  const int64_t hn = insulated(North) ? H_ : 0, hs = insulated(South) ? H_ : 0;
-  const int64_t hw = insulated(West) ? H_ : 0, he = insulated(East) ? H_ : 0;
+  auto ext = [&](int d) { return (insulated(d) || periodic(d)) ? int64_t(H_) : 0; };
+  const int64_t hn = ext(North), hs = ext(South), hw = ext(West), he = ext(East);
   g.gx0 = blk_.ox + hn;
   g.gy0 = blk_.oy + hw;
   g.nx = P_.nx + hn + hs;
@@ -932,10 +975,11 @@ std::pair<int64_t, int64_t> Solver::ensure_ghosts(int k, hipStream_t st) {
 void Solver::enqueue_pass(int k, int rl) {
   const auto& nb = blk_.nbr;
   const bool resid = rl > 0;
-  // With world > 1 every rank of the (non-periodic) grid has a neighbour.
+  // With world > 1 every rank of the grid has a neighbour.
   const bool multi = tr_->world() > 1;
-  // Ghosts to keep valid: neighbours' halos, or a plate's insulated sides.
-  const bool ghosts = multi || P_.insulated != 0;
+  // Ghosts to keep valid: neighbours' halos, or a plate's insulated sides and
+  // periodic axes.
+  const bool ghosts = multi || edge_ghosts();
   PassRec rec;
   rec.step0 = step_;
   rec.k = k;

@@ -63,23 +63,29 @@ int Cart::rank_of(int cx, int cy) const {
   return cx * py + cy;
 }
 
-std::array<int, 4> Cart::neighbors(int rank) const {
+int Cart::rank_of(int cx, int cy, unsigned periodic) const {
+  if ((periodic & kPeriodicX) && px > 1) cx = (cx + px) % px;
+  if ((periodic & kPeriodicY) && py > 1) cy = (cy + py) % py;
+  return rank_of(cx, cy);
+}
+
+std::array<int, 4> Cart::neighbors(int rank, unsigned periodic) const {
   auto c = coords(rank);
   std::array<int, 4> n{};
-  n[North] = rank_of(c[0] - 1, c[1]);
-  n[South] = rank_of(c[0] + 1, c[1]);
-  n[West] = rank_of(c[0], c[1] - 1);
-  n[East] = rank_of(c[0], c[1] + 1);
+  n[North] = rank_of(c[0] - 1, c[1], periodic);
+  n[South] = rank_of(c[0] + 1, c[1], periodic);
+  n[West] = rank_of(c[0], c[1] - 1, periodic);
+  n[East] = rank_of(c[0], c[1] + 1, periodic);
   return n;
 }
 
-std::array<int, 4> Cart::diagonal_neighbors(int rank) const {
+std::array<int, 4> Cart::diagonal_neighbors(int rank, unsigned periodic) const {
   auto c = coords(rank);
   std::array<int, 4> n{};
-  n[NorthWest] = rank_of(c[0] - 1, c[1] - 1);
-  n[NorthEast] = rank_of(c[0] - 1, c[1] + 1);
-  n[SouthWest] = rank_of(c[0] + 1, c[1] - 1);
-  n[SouthEast] = rank_of(c[0] + 1, c[1] + 1);
+  n[NorthWest] = rank_of(c[0] - 1, c[1] - 1, periodic);
+  n[NorthEast] = rank_of(c[0] - 1, c[1] + 1, periodic);
+  n[SouthWest] = rank_of(c[0] + 1, c[1] - 1, periodic);
+  n[SouthEast] = rank_of(c[0] + 1, c[1] + 1, periodic);
   return n;
 }
 
@@ -92,7 +98,7 @@ Span block_span(int64_t n, int parts, int index) {
   return s;
 }
 
-Block make_block(const Cart& cart, int rank, int64_t nx, int64_t ny) {
+Block make_block(const Cart& cart, int rank, int64_t nx, int64_t ny, unsigned periodic) {
   HEAT_CHECK(rank >= 0 && rank < cart.world, "rank %d of %d", rank, cart.world);
   Block b;
   b.rank = rank;
@@ -105,8 +111,8 @@ Block make_block(const Cart& cart, int rank, int64_t nx, int64_t ny) {
   b.lx = sx.size;
   b.oy = sy.offset;
   b.ly = sy.size;
-  b.nbr = cart.neighbors(rank);
-  b.diag = cart.diagonal_neighbors(rank);
+  b.nbr = cart.neighbors(rank, periodic);
+  b.diag = cart.diagonal_neighbors(rank, periodic);
   return b;
 }
 
@@ -125,7 +131,10 @@ Layout Layout::make(int64_t lx, int64_t ly, int halo) {
   return L;
 }
 
-Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated) {
+Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated,
+             unsigned periodic) {
+  // A periodic axis is decomposed and both its sides are open, as if insulated.
+  insulated |= periodic_sides(periodic);
   const bool ns = cart.px > 1 || (insulated & 3) != 0, ew = cart.py > 1 || (insulated & 12) != 0;
   auto open = [&](int d) { return b.nbr[size_t(d)] >= 0 || ((insulated >> d) & 1) != 0; };
   const int64_t gr = ns ? int64_t(m - 1) * depth : 0;
@@ -134,33 +143,36 @@ Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insula
              open(West) ? -gc : 0, b.ly + (open(East) ? gc : 0)};
 }
 
-int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated) {
+int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated,
+                          unsigned periodic) {
   const bool ins_x = (insulated & 3) != 0, ins_y = (insulated & 12) != 0;
+  const bool per_x = (periodic & kPeriodicX) != 0, per_y = (periodic & kPeriodicY) != 0;
   int64_t ext = INT64_MAX;
   for (int r = 0; r < cart.world; ++r) {
     const Block b = make_block(cart, r, nx, ny);
-    if (cart.px > 1 || ins_x) ext = std::min(ext, b.lx - (ins_x ? 1 : 0));
-    if (cart.py > 1 || ins_y) ext = std::min(ext, b.ly - (ins_y ? 1 : 0));
+    if (cart.px > 1 || ins_x || per_x) ext = std::min(ext, b.lx - (ins_x ? 1 : 0));
+    if (cart.py > 1 || ins_y || per_y) ext = std::min(ext, b.ly - (ins_y ? 1 : 0));
   }
   return ext;
 }
 
 int resident_halo_passes(const Cart& cart, int64_t nx, int64_t ny, int depth, int mmax,
-                         const std::function<int(const Box&)>& shape, unsigned insulated) {
-  if ((cart.world < 2 && insulated == 0) || depth < 1) return 0;
+                         const std::function<int(const Box&)>& shape, unsigned insulated,
+                         unsigned periodic) {
+  if ((cart.world < 2 && insulated == 0 && periodic == 0) || depth < 1) return 0;
   std::vector<Block> blocks;
   std::vector<int> own;
   for (int r = 0; r < cart.world; ++r) {
-    blocks.push_back(make_block(cart, r, nx, ny));
+    blocks.push_back(make_block(cart, r, nx, ny, periodic));
     const Block& b = blocks.back();
     own.push_back(shape(Box{0, b.lx, 0, b.ly}));
     if (own.back() == 0) return 0;
   }
-  const int64_t min_ext = halo_extent_limit(cart, nx, ny, insulated);
+  const int64_t min_ext = halo_extent_limit(cart, nx, ny, insulated, periodic);
   for (int m = int(std::min<int64_t>(mmax, min_ext / depth)); m >= 2; --m) {
     bool ok = true;
     for (size_t i = 0; i < blocks.size() && ok; ++i)
-      ok = shape(span_box(cart, blocks[i], depth, m, insulated)) == own[i];
+      ok = shape(span_box(cart, blocks[i], depth, m, insulated, periodic)) == own[i];
     if (ok) return m;
   }
   return 0;

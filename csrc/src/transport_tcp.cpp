@@ -198,16 +198,24 @@ class TcpTransport final : public Transport {
     for (int i = 0; i < n; ++i) {
       const Msg& m = msgs[i];
       HEAT_CHECK(m.peer >= 0 && m.peer < world_ && m.peer != rank_, "bad peer %d", m.peer);
-      for (auto& q : p) HEAT_CHECK(q.fd != fds_[size_t(m.peer)], "duplicate peer %d", m.peer);
       p.push_back({fds_[size_t(m.peer)], static_cast<const char*>(m.sbuf), m.sbytes,
                    static_cast<char*>(m.rbuf), m.rbytes});
     }
+    // Several messages may name one peer (both sides of a periodic axis with
+    // two ranks): they share its socket, so each direction of a message waits
+    // for the earlier messages of that peer, in list order.
+    auto turn = [&](size_t i, bool send) {
+      for (size_t j = 0; j < i; ++j)
+        if (p[j].fd == p[i].fd && (send ? p[j].sl : p[j].rl) != 0) return false;
+      return true;
+    };
     std::vector<pollfd> pf(p.size());
     while (true) {
       size_t active = 0;
       for (size_t i = 0; i < p.size(); ++i) {
         pf[i].fd = p[i].fd;
-        pf[i].events = short((p[i].sl ? POLLOUT : 0) | (p[i].rl ? POLLIN : 0));
+        pf[i].events = short(((p[i].sl && turn(i, true)) ? POLLOUT : 0) |
+                             ((p[i].rl && turn(i, false)) ? POLLIN : 0));
         pf[i].revents = 0;
         if (pf[i].events) ++active;
       }
@@ -217,7 +225,7 @@ class TcpTransport final : public Transport {
       for (size_t i = 0; i < p.size(); ++i) {
         if (pf[i].revents & (POLLERR | POLLNVAL))
           HEAT_CHECK(false, "tcp socket error");
-        if ((pf[i].revents & POLLOUT) && p[i].sl) {
+        if ((pf[i].revents & POLLOUT) && p[i].sl && turn(i, true)) {
           ssize_t k = ::send(p[i].fd, p[i].s, p[i].sl, MSG_NOSIGNAL);
           if (k > 0) {
             p[i].s += k;
@@ -226,7 +234,7 @@ class TcpTransport final : public Transport {
             HEAT_CHECK(errno == EAGAIN || errno == EINTR, "tcp send: %s", std::strerror(errno));
           }
         }
-        if ((pf[i].revents & (POLLIN | POLLHUP)) && p[i].rl) {
+        if ((pf[i].revents & (POLLIN | POLLHUP)) && p[i].rl && turn(i, false)) {
           ssize_t k = ::recv(p[i].fd, p[i].r, p[i].rl, 0);
           if (k > 0) {
             p[i].r += k;

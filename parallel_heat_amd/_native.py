@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch  # noqa: F401  (must be imported before libheat: shared HIP runtime)
 
-ABI_VERSION = 6  # must match HEAT_ABI_VERSION in csrc/include/heat/capi.h
+ABI_VERSION = 7  # must match HEAT_ABI_VERSION in csrc/include/heat/capi.h
 
 PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
@@ -52,7 +52,7 @@ class HeatParams(Structure):
         ("compat", c_int32), ("device", c_int32),
         ("schedule", c_int32), ("halo_passes", c_int32),
         ("numerics", c_int32), ("phase_timing", c_int32),
-        ("insulated", c_int32),
+        ("insulated", c_int32), ("periodic", c_int32),
     ]
 
 
@@ -98,6 +98,7 @@ class HeatBlockInfo(Structure):
         ("hx", c_int32), ("hy", c_int32), ("halo", c_int32), ("tb_depth", c_int32),
         ("bytes_per_field", c_int64),
         ("schedule", c_int32), ("insulated", c_int32),
+        ("periodic", c_int32), ("pad_", c_int32),
     ]
 
 
@@ -185,6 +186,10 @@ _SIGS = {
                                               c_void_p]),
     "heat_cpu_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int,
                                                c_int]),
+    "heat_op_fill_edge_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int, c_int,
+                                         c_void_p]),
+    "heat_cpu_fill_edge_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
+                                          c_int]),
     "heat_layout": (c_int, [c_int64, c_int64, c_int, POINTER(c_int64), POINTER(c_int64),
                             POINTER(c_int), POINTER(c_int)]),
     "heat_tb_supported": (c_int, [c_int]),

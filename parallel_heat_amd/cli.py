@@ -20,7 +20,7 @@ import sys
 import torch
 
 from . import _native
-from .models.config import HeatConfig, parse_insulated
+from .models.config import HeatConfig, check_edges, parse_insulated
 from .models.heat2d import HeatSolver
 from .parallel import comm as pcomm
 from .utils import io as hio
@@ -62,6 +62,9 @@ def build_parser() -> argparse.ArgumentParser:
     a("--insulated", default="", metavar="SIDES",
       help="insulated (zero-flux) plate edges: any of the letters nswe (n = row 0, w = column 0), "
            "or all; the other edges keep their temperature")
+    a("--periodic", default="", metavar="AXES",
+      help="periodic (wrap-around) axes: x (north and south edges joined), y (west and east "
+           "joined) or xy")
     a("--transport", choices=["auto", "local", "rccl", "torch", "tcp", "loopback"], default="auto",
       help="loopback: --gpus ranks sharing a device (native binary)")
     a("--port", type=int, default=0, help="tcp transport rendezvous port (0: MASTER_PORT+1)")
@@ -87,6 +90,7 @@ def main(argv=None) -> int:
     args = parser.parse_args(argv)
     try:
         parse_insulated(args.insulated)
+        check_edges(args.insulated, args.periodic)
     except ValueError as e:
         parser.error(str(e))
     if args.gpus > 0 or args.plan:
@@ -107,7 +111,8 @@ def main(argv=None) -> int:
                      px=args.px, py=args.py, use_graph=not args.no_graph,
                      overlap=not args.no_overlap, compat=compat, schedule=args.schedule,
                      halo_passes=args.halo_passes, numerics=args.numerics,
-                     phase_timing=args.phase_timing, insulated=args.insulated)
+                     phase_timing=args.phase_timing, insulated=args.insulated,
+                     periodic=args.periodic)
     info = pcomm.init_distributed("nccl" if backend == "hip" else "gloo")
     root = info.is_root
     out = sys.stdout
@@ -191,7 +196,7 @@ def main(argv=None) -> int:
                 transport=solver.transport, schedule=solver.info.schedule,
                 halo=solver.info.halo, t_exchange=acc["t_exchange"],
                 t_compute=acc["t_compute"], t_reduce=acc["t_reduce"],
-                insulated=solver.info.insulated,
+                insulated=solver.info.insulated, periodic=solver.info.periodic,
                 native=_native.loaded_path()) + "\n")
         out.flush()
     solver.barrier()

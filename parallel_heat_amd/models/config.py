@@ -37,6 +37,32 @@ def insulated_mask(sides: str) -> int:
     return sum(1 << SIDES.index(c) for c in parse_insulated(sides))
 
 
+AXES = "xy"  # x: rows (north and south edges joined), y: columns (west and east joined)
+
+
+def parse_periodic(axes: str) -> str:
+    """Normalise a periodic-axes value ("", "x", "y" or "xy", either order)
+    to its letters in x, y order; ValueError on anything else."""
+    if not isinstance(axes, str) or any(c not in AXES for c in axes):
+        raise ValueError(f"periodic={axes!r}; expected any of the letters {AXES!r}")
+    return "".join(c for c in AXES if c in axes)
+
+
+def periodic_mask(axes: str) -> int:
+    """Bit per axis (1 x, 2 y), as Params::periodic."""
+    return sum(1 << AXES.index(c) for c in parse_periodic(axes))
+
+
+def check_edges(insulated: str, periodic: str) -> None:
+    """An axis cannot be periodic and have an insulated side: ValueError
+    naming the axis."""
+    ins, per = parse_insulated(insulated), parse_periodic(periodic)
+    for axis, sides in (("x", "ns"), ("y", "we")):
+        if axis in per and any(c in ins for c in sides):
+            raise ValueError(f"axis {axis} is periodic (periodic={periodic!r}) and has an "
+                             f"insulated side (insulated={insulated!r}): choose one")
+
+
 @dataclass
 class HeatConfig:
     nx: int = 20                  # NXPROB (rows, slow index)
@@ -65,6 +91,7 @@ class HeatConfig:
     numerics: str = "fp32"        # fp32 (canonical FMA) | mpi (reference MPI double arithmetic)
     phase_timing: bool = False    # per-phase times (exchange/compute/reduce) in RunResult; eager
     insulated: str = ""           # insulated (zero-flux) plate edges: any of "nswe", or "all"
+    periodic: str = ""            # periodic (wrap-around) axes: "x" (north-south), "y", or "xy"
 
     def replace(self, **kw) -> "HeatConfig":
         return dataclasses.replace(self, **kw)
@@ -82,6 +109,7 @@ class HeatConfig:
         if self.halo_passes < 0:
             raise ValueError("halo_passes must be >= 0")
         parse_insulated(self.insulated)
+        check_edges(self.insulated, self.periodic)
 
     def total_steps(self) -> int:
         """Updates a full run performs (compat=mpi runs STEPS+1)."""
@@ -112,4 +140,5 @@ class HeatConfig:
         p.numerics = NUMERICS[self.numerics]
         p.phase_timing = int(bool(self.phase_timing))
         p.insulated = insulated_mask(self.insulated)
+        p.periodic = periodic_mask(self.periodic)
         return p

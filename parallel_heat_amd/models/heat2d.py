@@ -21,7 +21,7 @@ import numpy as np
 
 from .. import _native
 from ..parallel import comm as pcomm
-from .config import SIDES, HeatConfig
+from .config import AXES, SIDES, HeatConfig
 
 
 @dataclass
@@ -84,6 +84,7 @@ class BlockInfo:
     bytes_per_field: int
     schedule: str
     insulated: str = ""  # the run's insulated plate edges, letters of "nswe"
+    periodic: str = ""   # the run's periodic axes, letters of "xy"
 
 
 class HeatSolver:
@@ -168,7 +169,8 @@ class HeatSolver:
                          tuple(i.nbr), i.pitch, i.rows, i.hx, i.hy, i.halo, i.tb_depth,
                          i.bytes_per_field,
                          {1: "sync", 2: "overlap", 3: "pipeline"}.get(i.schedule, "?"),
-                         "".join(c for k, c in enumerate(SIDES) if i.insulated >> k & 1))
+                         "".join(c for k, c in enumerate(SIDES) if i.insulated >> k & 1),
+                         "".join(c for k, c in enumerate(AXES) if i.periodic >> k & 1))
 
     @property
     def step(self) -> int:

@@ -78,27 +78,58 @@ def insulated_sides(insulated: str) -> str:
     return insulated
 
 
-def _insulated_step(step, u, cx, cy, insulated):
+_AXES = "xy"  # x: rows (north and south edges joined), y: columns (west and east joined)
+
+
+def periodic_axes(periodic: str) -> str:
+    """"" | "x" | "y" | "xy" -> the letters, validated."""
+    if any(c not in _AXES for c in periodic):
+        raise ValueError(f"periodic={periodic!r}; expected any of the letters {_AXES!r}")
+    return periodic
+
+
+def _edge_pads(insulated: str, periodic: str):
+    """Per axis (rows, columns): (cells padded before, after, np.pad mode)."""
+    ins, per = insulated_sides(insulated), periodic_axes(periodic)
+    pads = []
+    for axis, (lo, hi) in zip(_AXES, ("ns", "we")):
+        if axis in per:
+            if lo in ins or hi in ins:
+                raise ValueError(f"axis {axis} is periodic and has an insulated side")
+            pads.append((1, 1, "wrap"))
+        else:
+            pads.append((int(lo in ins), int(hi in ins), "reflect"))
+    return pads
+
+
+def _edge_step(step, u, cx, cy, insulated, periodic=""):
     """One step with insulated (zero-flux) sides, the second-order mirror
-    scheme: the grid is padded by one cell beyond every insulated side with
-    its reflection across the edge row / column (u[-1, j] := u[1, j], the edge
-    cell not repeated; a corner between two insulated sides takes both), the
+    scheme, and periodic axes: the grid is padded by one cell beyond every
+    insulated side with its reflection across the edge row / column
+    (u[-1, j] := u[1, j], the edge cell not repeated; a corner between two
+    insulated sides takes both) and beyond both ends of every periodic axis
+    with the cell at the other end (u[-1, j] := u[nx-1, j], u[nx, j] :=
+    u[0, j]; an axis of extent 1 pads with itself), axis by axis, the
     Dirichlet step runs on the padded grid, whose ring it leaves fixed, and
-    the padding is cropped.  Edge cells of an insulated side are thereby
-    updated like interior cells; a corner shared with a Dirichlet side lies on
-    the padded grid's ring and stays fixed."""
-    ins = insulated_sides(insulated)
+    the padding is cropped.  Edge cells of such a side are thereby updated
+    like interior cells; a corner shared with a Dirichlet side lies on the
+    padded grid's ring and stays fixed."""
+    (n0, n1, mx), (w0, w1, my) = _edge_pads(insulated, periodic)
     u = np.asarray(u, np.float32)
-    pad = ((int("n" in ins), int("s" in ins)), (int("w" in ins), int("e" in ins)))
-    v = step(np.pad(u, pad, mode="reflect"), cx, cy)
+    p = np.pad(u, ((n0, n1), (0, 0)), mode=mx)
+    p = np.pad(p, ((0, 0), (w0, w1)), mode=my)
+    pad = ((n0, n1), (w0, w1))
+    v = step(p, cx, cy)
     return np.ascontiguousarray(v[pad[0][0]:v.shape[0] - pad[0][1], pad[1][0]:v.shape[1] - pad[1][1]])
 
 
-def step_np(u: np.ndarray, cx: float = 0.1, cy: float = 0.1, insulated: str = "") -> np.ndarray:
+def step_np(u: np.ndarray, cx: float = 0.1, cy: float = 0.1, insulated: str = "",
+            periodic: str = "") -> np.ndarray:
     """One Jacobi step in float32; boundary ring unchanged, except along the
-    `insulated` sides (letters of "nswe", or "all"; see _insulated_step)."""
-    if insulated:
-        return _insulated_step(step_np, u, cx, cy, insulated)
+    `insulated` sides (letters of "nswe", or "all") and the `periodic` axes
+    (letters of "xy"); see _edge_step."""
+    if insulated or periodic:
+        return _edge_step(step_np, u, cx, cy, insulated, periodic)
     u = np.asarray(u, np.float32)
     out = u.copy()
     if u.shape[0] < 3 or u.shape[1] < 3:
@@ -143,17 +174,18 @@ def fma32(a, b, c) -> np.ndarray:
 
 
 def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
-                insulated: str = "") -> np.ndarray:
+                insulated: str = "", periodic: str = "") -> np.ndarray:
     """One step with the engine's default numerics, bit for bit: the
     expression of ``heat::stencil`` with the same operands in the same order,
         tx = fma(-2, c, s + n);  ty = fma(-2, c, e + w)
         u' = fma(cy, ty, fma(cx, tx, c))
     (n / s: rows above / below, w / e: columns left / right; cx and cy rounded
     to float32 first, as HeatParams carries them); boundary ring unchanged,
-    except along the `insulated` sides (mirror scheme, _insulated_step: the
-    same expression, the missing neighbour being the cell's mirror image)."""
-    if insulated:
-        return _insulated_step(step_np_fma, u, cx, cy, insulated)
+    except along the `insulated` sides (mirror scheme, _edge_step: the same
+    expression, the missing neighbour being the cell's mirror image) and the
+    `periodic` axes (the missing neighbour: the cell at the other end)."""
+    if insulated or periodic:
+        return _edge_step(step_np_fma, u, cx, cy, insulated, periodic)
     u = np.asarray(u, np.float32)
     out = u.copy()
     if u.shape[0] < 3 or u.shape[1] < 3:
@@ -170,15 +202,15 @@ def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
 
 
 def step_np_mpi(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
-                insulated: str = "") -> np.ndarray:
+                insulated: str = "", periodic: str = "") -> np.ndarray:
     """One step with the reference MPI program's arithmetic
     (mpi/mpi_heat_improved_persistent_stat.c:168-174): the two neighbour sums
     in float32 (float + float in C), the rest in float64 because of the 2.0
     literal, evaluated left to right, rounded to float32 once.  NumPy float64
     ops are IEEE and never fused, so this is the exact oracle of
-    `numerics="mpi"`.  `insulated`: as step_np."""
-    if insulated:
-        return _insulated_step(step_np_mpi, u, cx, cy, insulated)
+    `numerics="mpi"`.  `insulated`, `periodic`: as step_np."""
+    if insulated or periodic:
+        return _edge_step(step_np_mpi, u, cx, cy, insulated, periodic)
     u = np.asarray(u, np.float32)
     out = u.copy()
     if u.shape[0] < 3 or u.shape[1] < 3:
@@ -193,23 +225,28 @@ def step_np_mpi(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
 
 
 def step_torch(u: torch.Tensor, cx: float = 0.1, cy: float = 0.1,
-               insulated: str = "") -> torch.Tensor:
-    """The same step as plain PyTorch fp32 ops (any device).  `insulated`: as
-    step_np."""
-    if insulated:
-        ins = insulated_sides(insulated)
+               insulated: str = "", periodic: str = "") -> torch.Tensor:
+    """The same step as plain PyTorch fp32 ops (any device).  `insulated`,
+    `periodic`: as step_np."""
+    if insulated or periodic:
+        (n0, n1, mx), (w0, w1, my) = _edge_pads(insulated, periodic)
         p = u
-        if "n" in ins:
-            p = torch.cat([p[1:2], p], 0)
-        if "s" in ins:
-            p = torch.cat([p, p[-2:-1]], 0)
-        if "w" in ins:
-            p = torch.cat([p[:, 1:2], p], 1)
-        if "e" in ins:
-            p = torch.cat([p, p[:, -2:-1]], 1)
+        if mx == "wrap":
+            p = torch.cat([p[-1:], p, p[:1]], 0)
+        else:
+            if n0:
+                p = torch.cat([p[1:2], p], 0)
+            if n1:
+                p = torch.cat([p, p[-2:-1]], 0)
+        if my == "wrap":
+            p = torch.cat([p[:, -1:], p, p[:, :1]], 1)
+        else:
+            if w0:
+                p = torch.cat([p[:, 1:2], p], 1)
+            if w1:
+                p = torch.cat([p, p[:, -2:-1]], 1)
         v = step_torch(p, cx, cy)
-        return v[int("n" in ins):v.shape[0] - int("s" in ins),
-                 int("w" in ins):v.shape[1] - int("e" in ins)].clone()
+        return v[n0:v.shape[0] - n1, w0:v.shape[1] - w1].clone()
     out = u.clone()
     if u.shape[0] < 3 or u.shape[1] < 3:
         return out
@@ -231,18 +268,20 @@ def run_np(nx: int, ny: int, steps: int, cx: float = 0.1, cy: float = 0.1,
            converge: bool = False, check_interval: int = 20, eps: float = 1e-3,
            compat: str = "none", init: str = "ref-wrap", seed: int = 0,
            u0: Optional[np.ndarray] = None,
-           numerics: str = "fp32", insulated: str = "") -> Tuple[np.ndarray, int, int]:
+           numerics: str = "fp32", insulated: str = "",
+           periodic: str = "") -> Tuple[np.ndarray, int, int]:
     """Run the model; returns (grid, steps_done, converged_at or -1).
     numerics: "fp32" (plain float32, a few ulps from the engine), "fma" (the
     engine's default numerics, exact) or "mpi" (its numerics="mpi", exact).
     insulated: the plate's insulated (zero-flux) sides, letters of "nswe" or
-    "all"; the residual then covers their edge cells too."""
+    "all"; periodic: its periodic axes, letters of "xy"; the residual then
+    covers their edge cells too."""
     step = {"fp32": step_np, "fma": step_np_fma, "mpi": step_np_mpi}[numerics]
     u = init_grid(nx, ny, init, seed) if u0 is None else np.array(u0, np.float32)
     total = steps + 1 if compat == "mpi" else steps
     checks = set(check_points(total, check_interval, compat)) if converge else set()
     for k in range(1, total + 1):
-        v = step(u, cx, cy, insulated) if insulated else step(u, cx, cy)
+        v = step(u, cx, cy, insulated, periodic) if insulated or periodic else step(u, cx, cy)
         if k in checks:
             r = float(np.max(np.abs(v - u))) if v.size else 0.0
             ok = r <= eps if compat == "mpi" else r < np.float32(eps)

@@ -19,7 +19,7 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from .. import _native
-from ..models.config import INIT_MODES, insulated_mask
+from ..models.config import INIT_MODES, check_edges, insulated_mask, periodic_mask
 from ..parallel.topology import layout
 
 Box = Tuple[int, int, int, int]  # (r0, r1, c0, c1) in local coordinates
@@ -284,6 +284,30 @@ def fill_insulated_ghosts(f: Field, sides: str, depth: int) -> None:
         return
     _native.call("heat_op_fill_insulated_ghosts", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly,
                  mask, depth, ctypes.c_void_p(_stream()))
+
+
+def fill_edge_ghosts(f: Field, insulated: str, periodic: str, depth: int) -> None:
+    """The general fill of the field's ghost frame, `depth` cells deep: the
+    mirror image beyond every side in `insulated` (as fill_insulated_ghosts),
+    the field's opposite edge beyond both sides of every axis in `periodic`
+    (letters of "xy": (r < 0, c) := (r + lx, c), (r >= lx, c) := (r - lx, c),
+    likewise for columns), composed per axis in the corners.  An axis cannot be
+    wrapped and mirrored; a wrapped axis needs an extent >= depth.  One HIP
+    launch on a GPU field; the host twin the CPU backend uses on a CPU field."""
+    check_edges(insulated, periodic)
+    ins, per = insulated_mask(insulated), periodic_mask(periodic)
+    if depth < 1 or depth > f.halo:
+        raise ValueError(f"depth {depth} outside the field's ghost ring ({f.halo})")
+    if (ins & 3 and f.lx <= depth) or (ins & 12 and f.ly <= depth):
+        raise ValueError(f"a {f.lx} x {f.ly} field cannot mirror {depth} rows/columns")
+    if (per & 1 and f.lx < depth) or (per & 2 and f.ly < depth):
+        raise ValueError(f"a {f.lx} x {f.ly} field cannot wrap {depth} rows/columns")
+    if f.device.type == "cpu":
+        _native.call("heat_cpu_fill_edge_ghosts", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly,
+                     ins, per, depth)
+        return
+    _native.call("heat_op_fill_edge_ghosts", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly,
+                 ins, per, depth, ctypes.c_void_p(_stream()))
 
 
 def residual(a: Field, b: Field, box: Optional[Box] = None,

@@ -130,6 +130,7 @@ def resident_fits(rows: int, cols: int, depth: int = 12) -> bool:
 
 
 RES_MIN_PASSES = 4  # csrc/include/heat/plan.hpp kResMinPasses
+FILL_US = 12.0      # one ghost-fill launch of a deep frame (profiles/periodic_overhead.md)
 
 
 def _blocks(n: int, parts: int) -> List[int]:
@@ -138,28 +139,32 @@ def _blocks(n: int, parts: int) -> List[int]:
 
 
 def resident_halo_passes(nx: int, ny: int, px: int, py: int, depth: int = 12,
-                         mmax: int = 8) -> int:
+                         mmax: int = 8, periodic: str = "") -> int:
     """The solver's resident-aware passes per exchange (topology.cpp
     resident_halo_passes): the largest m in [2, mmax] for which every rank's
     first span box -- the owned block grown by (m - 1) * depth on each side
     with a neighbour -- has a one-round resident plan of the same tile shape
     as its owned block's; 0 if the owned blocks have none or no m keeps it.
-    The solver keeps m = 8 below RES_MIN_PASSES."""
-    if px * py < 2:
+    The solver keeps m = 8 below RES_MIN_PASSES.  `periodic` (letters of
+    "xy"): a periodic axis counts as decomposed, also with one rank along it,
+    and both sides of every block along it as sides with a neighbour."""
+    per_x, per_y = "x" in periodic, "y" in periodic
+    if px * py < 2 and not (per_x or per_y):
         return 0
+    ns, ew = px > 1 or per_x, py > 1 or per_y
     rows, cols = _blocks(nx, px), _blocks(ny, py)
     own = {(r, c): resident_shape(r, c, depth) for r in rows for c in cols}
     if any(v is None for v in own.values()):
         return 0
-    ext = min((rows if px > 1 else []) + (cols if py > 1 else []))
+    ext = min((rows if ns else []) + (cols if ew else []))
     for m in range(min(mmax, ext // depth), 1, -1):
-        gr = (m - 1) * depth if px > 1 else 0
-        gc = ((m - 1) * depth) // 4 * 4 if py > 1 else 0
+        gr = (m - 1) * depth if ns else 0
+        gc = ((m - 1) * depth) // 4 * 4 if ew else 0
         ok = True
         for i, r in enumerate(rows):
             for j, c in enumerate(cols):
-                er = gr * ((i > 0) + (i < px - 1))
-                ec = gc * ((j > 0) + (j < py - 1))
+                er = gr * (2 if per_x else (i > 0) + (i < px - 1))
+                ec = gc * (2 if per_y else (j > 0) + (j < py - 1))
                 ok = ok and resident_shape(r + er, c + ec, depth) == own[(r, c)]
         if ok:
             return m
@@ -262,38 +267,51 @@ def predict(cfg: HeatConfig, world: int, depth: int = 12, halo_passes: int = 8,
     px, py = _grid(cfg, world)
     lx = math.ceil(cfg.nx / px)
     ly = math.ceil(cfg.ny / py)
+    # Periodic axes have ghosts too (a neighbour's halo, or the block's own
+    # opposite edge): the halo rule of a decomposed axis, also on one GPU, the
+    # sync schedule, and a ghost depth of at most the block extent.
+    per_x, per_y = "x" in cfg.periodic, "y" in cfg.periodic
+    ghosts = world > 1 or per_x or per_y
     m = cfg.halo_passes or halo_passes
-    if not cfg.halo_passes and world > 1:
-        rm = resident_halo_passes(cfg.nx, cfg.ny, px, py, depth)
+    if not cfg.halo_passes and ghosts:
+        rm = resident_halo_passes(cfg.nx, cfg.ny, px, py, depth, periodic=cfg.periodic)
         if rm >= RES_MIN_PASSES:
             m = rm
-    if world == 1:
+    if not ghosts:
         m = 1
     schedule = cfg.schedule if cfg.schedule != "auto" else "sync"
+    if per_x or per_y:
+        schedule = "sync"
+        m = max(1, min([m] + [(cfg.nx // px) // depth] * per_x + [(cfg.ny // py) // depth] * per_y))
     if world > 1 and schedule != "sync":
         m = 1
     H = m * depth
     # Deep-halo ghost rows recomputed on the decomposed axes: the first
     # pass's box (resident launches keep it for all m passes) grows by H - K
     # per neighbour side, two for an inner rank (p > 2), one with p = 2.
-    ext_r = (2 if px > 2 else 1) * (H - depth) if px > 1 else 0
-    ext_c = (2 if py > 2 else 1) * (H - depth) if py > 1 else 0
+    # Along a periodic axis every rank has two.
+    ext_r = (2 if px > 2 or per_x else 1) * (H - depth) if px > 1 or per_x else 0
+    ext_c = (2 if py > 2 or per_y else 1) * (H - depth) if py > 1 or per_y else 0
     resident = schedule == "sync" and resident_fits(lx + ext_r, ly + ext_c, depth)
     if resident:
         # The span box's long-span rate, less the span's load / store.
         rate = rate_tcells(lx + ext_r, ly + ext_c, True) * 1e12
-        if world > 1:
+        if ghosts:
             rate /= 1.0 + SPAN_COST / m
     else:
         rate = rate_tcells(lx, ly, False) * 1e12
     cells = (lx + ext_r) * (ly + ext_c)
     compute_s = cells * 1000 / rate
-    exchanges = math.ceil(1000 / H) if world > 1 else 0
+    exchanges = math.ceil(1000 / H) if ghosts else 0
     ns_bytes = H * (ly + 2 * H) * 4 if px > 1 else 0
     ew_bytes = lx * H * 4 if py > 1 else 0
     msg = max(ns_bytes, ew_bytes)
     t_ex = (X["latency_us"] * 1e-6 + msg / (X["link_gbps"] * 1e9) +
             (2 * X["pack_us"] * 1e-6 if py > 1 else 0.0))
+    if world == 1:
+        # A periodic plate on one GPU: the exchange is the ghost-fill launch
+        # (profiles/periodic_overhead.md: 7-12 us).
+        t_ex = FILL_US * 1e-6
     ex_total = exchanges * t_ex
     if schedule != "sync" and world > 1:
         # Overlap schedules: one K-deep exchange per pass, hidden behind the

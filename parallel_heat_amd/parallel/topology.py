@@ -91,23 +91,34 @@ class Cart:
             return cx * self.py + cy
         return NO_NEIGHBOR
 
-    def neighbors(self, rank: int) -> Tuple[int, int, int, int]:
-        cx, cy = self.coords(rank)
-        return (self.rank_of(cx - 1, cy), self.rank_of(cx + 1, cy),
-                self.rank_of(cx, cy - 1), self.rank_of(cx, cy + 1))
+    def _wrapped(self, cx: int, cy: int, periodic: int) -> int:
+        """rank_of with the coordinate wrapped along every periodic axis
+        (`periodic`: bit 0 = x, bit 1 = y, as Params::periodic) that has more
+        than one rank; with one rank along it the neighbour stays
+        NO_NEIGHBOR (the rank fills its own ghosts)."""
+        if periodic & 1 and self.px > 1:
+            cx %= self.px
+        if periodic & 2 and self.py > 1:
+            cy %= self.py
+        return self.rank_of(cx, cy)
 
-    def diagonal_neighbors(self, rank: int) -> Tuple[int, int, int, int]:
+    def neighbors(self, rank: int, periodic: int = 0) -> Tuple[int, int, int, int]:
+        cx, cy = self.coords(rank)
+        return (self._wrapped(cx - 1, cy, periodic), self._wrapped(cx + 1, cy, periodic),
+                self._wrapped(cx, cy - 1, periodic), self._wrapped(cx, cy + 1, periodic))
+
+    def diagonal_neighbors(self, rank: int, periodic: int = 0) -> Tuple[int, int, int, int]:
         """(NW, NE, SW, SE): the owners of the ghost corners of deep halos
         (heat::Cart::diagonal_neighbors)."""
         cx, cy = self.coords(rank)
-        return (self.rank_of(cx - 1, cy - 1), self.rank_of(cx - 1, cy + 1),
-                self.rank_of(cx + 1, cy - 1), self.rank_of(cx + 1, cy + 1))
+        return (self._wrapped(cx - 1, cy - 1, periodic), self._wrapped(cx - 1, cy + 1, periodic),
+                self._wrapped(cx + 1, cy - 1, periodic), self._wrapped(cx + 1, cy + 1, periodic))
 
-    def block(self, rank: int, nx: int, ny: int) -> Block:
+    def block(self, rank: int, nx: int, ny: int, periodic: int = 0) -> Block:
         cx, cy = self.coords(rank)
         ox, lx = block_span(nx, self.px, cx)
         oy, ly = block_span(ny, self.py, cy)
-        return Block(rank, cx, cy, ox, oy, lx, ly, self.neighbors(rank))
+        return Block(rank, cx, cy, ox, oy, lx, ly, self.neighbors(rank, periodic))
 
 
 def layout(lx: int, ly: int, halo: int) -> Tuple[int, int, int, int]:
