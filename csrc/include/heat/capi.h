@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define HEAT_ABI_VERSION 7
+#define HEAT_ABI_VERSION 8
 
 typedef struct heat_params {
   int64_t nx, ny;
@@ -212,6 +212,21 @@ int heat_op_unpack(const float* buf, float* origin, int64_t pitch, int64_t r0, i
                    int64_t c0, int64_t c1, void* stream);
 int heat_op_residual(const float* a, const float* b, int64_t pitch, int64_t r0, int64_t r1,
                      int64_t c0, int64_t c1, unsigned* resid, void* stream);
+/* n <= 8 boxes (r0, r1, c0, c1 each) <-> their contiguous device buffers in one
+   launch (the packing / unpacking of a halo exchange); empty boxes are skipped. */
+int heat_op_copy_boxes(float* origin, int64_t pitch, const int64_t* boxes /* n*4 */,
+                       float* const* bufs /* n device pointers */, int n, int to_buf, void* stream);
+/* The device-side convergence decision (heat::gpu::judge_check): `gate` is an
+   8-word device record {stop, reason, stop_check, checks, last_bits, pad[3]};
+   check i of the n is the max over s < slots of resid[s * stride + i]. */
+int heat_op_judge(unsigned* resid, void* gate, double eps, int mpi_compat, int n, int slots,
+                  int stride, void* stream);
+/* Checksum of an lx x ly block whose cell (0,0) is cell (ox, oy) of a plate with
+   ny columns: the device kernel (waits for it), and its host twin on host memory. */
+int heat_op_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                     int64_t oy, int64_t ny, heat_checksum* out, void* stream);
+int heat_cpu_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                      int64_t oy, int64_t ny, heat_checksum* out);
 /* Mirror an lx x ly field into its `depth`-deep ghost frame beyond the insulated
    sides in `sides` (1 north, 2 south, 4 west, 8 east): the device kernel, and
    its host twin on host memory. */

@@ -64,7 +64,12 @@ class Transport {
   virtual bool graph_capturable() const { return false; }
   // All messages of one call progress concurrently (grouped).
   virtual void sendrecv(const Msg* msgs, int n, hipStream_t st) = 0;
-  // In-place max over ranks of `count` floats.
+  // In-place max over ranks of `count` floats (any sign).  The max propagates
+  // NaN: if any rank holds a NaN in an element, every rank ends with a NaN
+  // there (the convergence decision relies on it: a rank's non-finite
+  // residual must stop the run on every rank, never be reduced to a peer's
+  // small finite one); -0 and +0 may come back as either.  The callback
+  // transport leaves this to the embedding program's `allreduce` (dtype 0).
   virtual void allreduce_max(float* buf, int count, hipStream_t st) = 0;
   // In-place sum over ranks of `count` doubles / uint64 (host or device per device_memory()).
   virtual void allreduce_sum_f64(double* buf, int count, hipStream_t st) = 0;

@@ -607,6 +607,64 @@ int heat_op_residual(const float* a, const float* b, int64_t pitch, int64_t r0, 
   });
 }
 
+int heat_op_copy_boxes(float* origin, int64_t pitch, const int64_t* boxes, float* const* bufs, int n,
+                       int to_buf, void* stream) {
+  return guard([&] {
+    HEAT_CHECK(n >= 0 && n <= heat::gpu::kMaxBoxCopies, "copy_boxes: %d boxes", n);
+    heat::gpu::BoxCopy c[heat::gpu::kMaxBoxCopies];
+    for (int i = 0; i < n; ++i)
+      c[i] = {heat::Box{boxes[4 * i], boxes[4 * i + 1], boxes[4 * i + 2], boxes[4 * i + 3]}, bufs[i]};
+    heat::gpu::copy_boxes(origin, pitch, c, n, to_buf != 0, S(stream));
+  });
+}
+
+int heat_op_judge(unsigned* resid, void* gate, double eps, int mpi_compat, int n, int slots,
+                  int stride, void* stream) {
+  return guard([&] {
+    static_assert(sizeof(heat::gpu::DeviceGate) == 32, "DeviceGate is 8 words");
+    heat::gpu::judge_check(resid, static_cast<heat::gpu::DeviceGate*>(gate), eps, mpi_compat != 0,
+                           S(stream), n, slots, stride);
+  });
+}
+
+int heat_op_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                     int64_t oy, int64_t ny, heat_checksum* out, void* stream) {
+  return guard([&] {
+    // As Solver::checksum: a zeroed device record, one launch, keys decoded.
+    heat::gpu::DeviceChecksum* d = nullptr;
+    HIP_CHECK(hipMalloc(&d, sizeof *d));
+    heat::gpu::DeviceChecksum h{0, 0.0, 0x7FFFFFFF, int(0x80000000), 0};
+    hipError_t e = hipMemcpyAsync(d, &h, sizeof h, hipMemcpyHostToDevice, S(stream));
+    try {
+      HIP_CHECK(e);
+      heat::gpu::checksum_block(origin, pitch, lx, ly, ox, oy, ny, d, S(stream));
+      HIP_CHECK(hipMemcpyAsync(&h, d, sizeof h, hipMemcpyDeviceToHost, S(stream)));
+      HIP_CHECK(hipStreamSynchronize(S(stream)));
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    HIP_CHECK(hipFree(d));
+    out->hash = h.hash;
+    out->sum = h.sum;
+    out->count = int64_t(h.count);
+    out->min = heat::gpu::checksum_key_to_float(h.min_key);
+    out->max = heat::gpu::checksum_key_to_float(h.max_key);
+  });
+}
+
+int heat_cpu_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                      int64_t oy, int64_t ny, heat_checksum* out) {
+  return guard([&] {
+    const heat::Checksum c = heat::checksum_block(origin, pitch, ox, oy, lx, ly, ny);
+    out->hash = c.hash;
+    out->sum = c.sum;
+    out->min = c.min;
+    out->max = c.max;
+    out->count = c.count;
+  });
+}
+
 int heat_op_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,
                                   int depth, void* stream) {
   return guard([&] {

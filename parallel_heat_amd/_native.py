@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch  # noqa: F401  (must be imported before libheat: shared HIP runtime)
 
-ABI_VERSION = 7  # must match HEAT_ABI_VERSION in csrc/include/heat/capi.h
+ABI_VERSION = 8  # must match HEAT_ABI_VERSION in csrc/include/heat/capi.h
 
 PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
@@ -182,6 +182,14 @@ _SIGS = {
                                c_void_p]),
     "heat_op_residual": (c_int, [c_void_p, c_void_p, c_int64, c_int64, c_int64, c_int64,
                                  c_int64, c_void_p, c_void_p]),
+    "heat_op_copy_boxes": (c_int, [c_void_p, c_int64, POINTER(c_int64), POINTER(c_void_p), c_int,
+                                   c_int, c_void_p]),
+    "heat_op_judge": (c_int, [c_void_p, c_void_p, c_double, c_int, c_int, c_int, c_int,
+                              c_void_p]),
+    "heat_op_checksum": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                 POINTER(HeatChecksum), c_void_p]),
+    "heat_cpu_checksum": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
+                                  POINTER(HeatChecksum)]),
     "heat_op_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
                                               c_void_p]),
     "heat_cpu_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int,

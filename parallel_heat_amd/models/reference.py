@@ -66,6 +66,36 @@ def init_grid(nx: int, ny: int, mode: str = "ref-wrap", seed: int = 0,
     raise ValueError(mode)
 
 
+def checksum_np(block: np.ndarray, ox: int = 0, oy: int = 0, ny: Optional[int] = None) -> dict:
+    """The engine's checksum of a block whose cell (0, 0) is cell (ox, oy) of a
+    plate with `ny` columns (default: the block's own), computed independently:
+    hash = sum of mix64(global index * 0x100000001B3 ^ float bits) mod 2^64
+    over uint64 arrays, count / min / max from the float values (NaN as NumPy
+    orders it: it wins both), sum from math.fsum (exactly rounded, so any
+    summation order of the engine lies within the fp64 worst-case bound of
+    it).  Same keys as ops.checksum."""
+    import math
+
+    b = np.ascontiguousarray(block, np.float32)
+    lx, ly = b.shape
+    ny = ly if ny is None else int(ny)
+    with np.errstate(over="ignore"):
+        gidx = ((_U64(ox) + np.arange(lx, dtype=np.uint64))[:, None] * _U64(ny)
+                + (_U64(oy) + np.arange(ly, dtype=np.uint64))[None, :])
+        h = _mix64(gidx * _U64(0x100000001B3) ^ b.view(np.uint32).astype(np.uint64))
+        total = int(np.add.reduce(h.ravel(), dtype=np.uint64)) if h.size else 0
+    vals = b.astype(np.float64).ravel().tolist()
+    with np.errstate(invalid="ignore"):
+        mn = float(b.min()) if b.size else float("inf")
+        mx = float(b.max()) if b.size else float("-inf")
+    try:
+        s = math.fsum(vals)
+    except (OverflowError, ValueError):  # +inf and -inf both present, or overflow
+        with np.errstate(invalid="ignore", over="ignore"):
+            s = float(np.sum(b.astype(np.float64)))
+    return {"hash": total, "sum": s, "min": mn, "max": mx, "count": int(b.size)}
+
+
 _SIDES = "nswe"  # north = row 0, south = last row, west = column 0, east = last column
 
 

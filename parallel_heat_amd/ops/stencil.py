@@ -266,6 +266,99 @@ def unpack(buf: torch.Tensor, f: Field, box: Box) -> None:
                  f.pitch, r0, r1, c0, c1, ctypes.c_void_p(_stream()))
 
 
+MAX_BOX_COPIES = 8  # heat::gpu::kMaxBoxCopies
+
+
+def copy_boxes(f: Field, copies: Sequence[Tuple[Box, torch.Tensor]], to_buf: bool) -> None:
+    """Up to MAX_BOX_COPIES boxes of `f` to (to_buf) or from their contiguous
+    buffers (row-major rows x cols each) in ONE launch: the packing /
+    unpacking of a whole halo exchange (heat::gpu::copy_boxes).  Empty boxes
+    are skipped.  On a CPU field, the slicing of pack / unpack per box."""
+    copies = list(copies)
+    if f.device.type == "cpu":
+        if len(copies) > MAX_BOX_COPIES:
+            raise ValueError(f"copy_boxes: {len(copies)} boxes")
+        for (r0, r1, c0, c1), buf in copies:
+            if r1 > r0 and c1 > c0:
+                (pack(f, (r0, r1, c0, c1), buf) if to_buf else unpack(buf, f, (r0, r1, c0, c1)))
+        return
+    n = len(copies)
+    for (r0, r1, c0, c1), buf in copies:
+        if buf.dtype != torch.float32 or buf.device != f.device or not buf.is_contiguous():
+            raise ValueError("buffers must be contiguous float32 tensors on the field's device")
+        if buf.numel() < max(0, r1 - r0) * max(0, c1 - c0):
+            raise ValueError(f"buffer of {buf.numel()} floats for box {(r0, r1, c0, c1)}")
+        if r1 > r0 and c1 > c0 and (r0 < -f.hx or r1 > f.rows - f.hx or c0 < -f.hy
+                                    or c1 > f.pitch - f.hy):
+            raise ValueError(f"box {(r0, r1, c0, c1)} outside the field's allocation")
+    boxes = (ctypes.c_int64 * (4 * n))(*[v for b, _ in copies for v in b])
+    bufs = (ctypes.c_void_p * n)(*[buf.data_ptr() for _, buf in copies])
+    _native.call("heat_op_copy_boxes", ctypes.c_void_p(f.ptr()), f.pitch, boxes, bufs, n,
+                 int(bool(to_buf)), ctypes.c_void_p(_stream()))
+
+
+@dataclass
+class Gate:
+    """The device gate record (``heat::gpu::DeviceGate``, 8 int32 words of
+    which the last three are padding)."""
+    stop: int = 0        # non-zero once closed
+    reason: int = 0      # 1 converged, 2 non-finite residual
+    stop_check: int = 0  # ordinal of the closing check
+    checks: int = 0      # checks judged while open
+    last_bits: int = 0   # residual (float bits) of the last judged check
+
+    WORDS = 8
+
+    def tensor(self, device) -> torch.Tensor:
+        w = [self.stop, self.reason, self.stop_check, self.checks, self.last_bits, 0, 0, 0]
+        return torch.tensor(w, dtype=torch.int64).to(torch.int32).to(device)
+
+    @classmethod
+    def read(cls, gate: torch.Tensor) -> "Gate":
+        w = [int(v) & 0xFFFFFFFF for v in gate[:5].cpu().tolist()]
+        return cls(*w)
+
+
+def judge(resid: torch.Tensor, gate: torch.Tensor, eps: float, mpi_compat: bool = False,
+          n: int = 1, slots: int = 1, stride: int = 0) -> None:
+    """The device-side convergence decision (heat::gpu::judge_check, GPU only)
+    on n checks in order: check i's residual is the maximum, as unsigned
+    words, of resid[s * stride + i] over s < slots; while the gate (an 8-word
+    int32 tensor laid out as Gate) is open, a non-finite word closes it with
+    reason 2, a word that meets eps (mpi_compat: double(r) <= eps, otherwise
+    r < float32(eps)) with reason 1.  The words read are zeroed either way."""
+    if resid.dtype != torch.int32 or gate.dtype != torch.int32:
+        raise ValueError("resid and gate must be int32 tensors")
+    if resid.device.type != "cuda" or gate.device != resid.device:
+        raise ValueError("judge needs GPU tensors on one device")
+    if gate.numel() < Gate.WORDS or not gate.is_contiguous() or not resid.is_contiguous():
+        raise ValueError("gate must hold 8 contiguous words, resid be contiguous")
+    if n >= 1 and 1 <= slots <= 64 and stride >= 0 and \
+            resid.numel() < (slots - 1) * stride + n:
+        raise ValueError(f"{resid.numel()} residual words for {n} checks x {slots} slots")
+    _native.call("heat_op_judge", ctypes.c_void_p(resid.data_ptr()),
+                 ctypes.c_void_p(gate.data_ptr()), float(eps), int(bool(mpi_compat)), int(n),
+                 int(slots), int(stride), ctypes.c_void_p(_stream()))
+
+
+def checksum(f: Field, ox: int = 0, oy: int = 0, ny: Optional[int] = None) -> dict:
+    """Checksum of the field's owned block placed at (ox, oy) of a plate with
+    `ny` columns (default: the block's own): {"hash": wrapping u64 sum of
+    mix64(global index * 0x100000001B3 ^ bits) as an int, "sum" (float64),
+    "min", "max", "count"}.  The device kernel on a GPU field (its sum follows
+    no fixed order), the host heat::checksum_block on a CPU field.  Hashes and
+    counts of disjoint blocks add up to the plate's."""
+    ny = f.ly if ny is None else int(ny)
+    c = _native.HeatChecksum()
+    if f.device.type == "cpu":
+        _native.call("heat_cpu_checksum", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly, int(ox),
+                     int(oy), ny, ctypes.byref(c))
+    else:
+        _native.call("heat_op_checksum", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly, int(ox),
+                     int(oy), ny, ctypes.byref(c), ctypes.c_void_p(_stream()))
+    return {"hash": int(c.hash), "sum": c.sum, "min": c.min, "max": c.max, "count": int(c.count)}
+
+
 def fill_insulated_ghosts(f: Field, sides: str, depth: int) -> None:
     """Insulated (zero-flux) plate edges: fill the field's ghost frame, `depth`
     cells deep, beyond every side in `sides` (letters of "nswe", or "all")

@@ -111,8 +111,18 @@ class TorchDistTransport:
     def _allreduce(self, ctx, buf, count, dtype):
         try:
             if dtype == 0:
-                a = _np_view(buf, 4 * count, np.float32)
-                op = dist.ReduceOp.MAX
+                # The max must propagate NaN (heat::Transport::allreduce_max);
+                # gloo's float MAX does not (of [1, NaN, 3] it can return 1).
+                # So: every NaN to +NaN, floats to the order-preserving int32
+                # key (float_key in csrc/kernels/stencil.hip, its own
+                # inverse), where +NaN lies above +inf; integer MAX; back.
+                a = _np_view(buf, 4 * count, np.int32)
+                k = np.where(np.isnan(a.view(np.float32)), np.int32(0x7FC00000), a)
+                t = torch.from_numpy(np.where(k >= 0, k, k ^ np.int32(0x7FFFFFFF)))
+                dist.all_reduce(t, op=dist.ReduceOp.MAX, group=self.group)
+                k = t.numpy()
+                a[:] = np.where(k >= 0, k, k ^ np.int32(0x7FFFFFFF))
+                return 0
             elif dtype == 1:
                 a = _np_view(buf, 8 * count, np.float64)
                 op = dist.ReduceOp.SUM

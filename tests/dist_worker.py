@@ -114,6 +114,58 @@ def run_create(world, cfg_kwargs, tmp_path):
     return [(tmp_path / f"create_{r}.txt").read_text() for r in range(world)]
 
 
+def run_outcome(s, grid, steps):
+    """Scatter `grid` (rank 0 holds it), run, and say what came of it: the
+    error's text, "converged at N" or "ran N"."""
+    try:
+        s.scatter(grid if s.rank == 0 else None)
+        r = s.run(steps)
+        return f"converged at {r.converged_at}" if r.converged else f"ran {r.steps_done}"
+    except Exception as e:  # noqa: BLE001 - the text is the result
+        return f"{type(e).__name__}: {e}"
+
+
+def outcome_worker(rank, world, port, cfg_kwargs, steps, grid_path, out_dir, transport, env):
+    """Every rank runs `steps` steps from the grid saved at grid_path (rank 0
+    scatters it) and writes run_outcome's text into a file of its own.  As in
+    create_worker no rank waits for another after the run: ranks that disagree
+    show up as differing files."""
+    import torch.distributed as dist
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
+                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    os.environ.update(env or {})
+    if transport == "rccl":
+        rccl_host_per_rank(rank)
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from parallel_heat_amd import HeatConfig, HeatSolver
+    from parallel_heat_amd.parallel.comm import DistInfo
+
+    cfg = HeatConfig(**cfg_kwargs)
+    try:
+        s = HeatSolver(cfg, transport=transport, dist_info=DistInfo(rank, world, rank),
+                       device=0 if cfg.backend == "hip" else None)
+        text = run_outcome(s, np.load(grid_path) if rank == 0 else None, steps)
+    except Exception as e:  # noqa: BLE001
+        s, text = None, f"create {type(e).__name__}: {e}"
+    with open(os.path.join(out_dir, f"outcome_{rank}.txt"), "w") as f:
+        f.write(text)
+    if s is not None:
+        s.close()
+    dist.destroy_process_group()
+
+
+def run_outcomes(world, cfg_kwargs, steps, grid, tmp_path, transport="torch", env=None):
+    """run_outcome's text of every rank of a world of processes."""
+    import torch.multiprocessing as mp
+
+    grid_path = str(tmp_path / "start.npy")
+    np.save(grid_path, grid)
+    mp.spawn(outcome_worker, args=(world, free_port(), cfg_kwargs, steps, grid_path,
+                                   str(tmp_path), transport, env), nprocs=world, join=True)
+    return [(tmp_path / f"outcome_{r}.txt").read_text() for r in range(world)]
+
+
 def tune_worker(rank, world, port, cfg_kwargs, out_path, transport):
     """Runs parallel.tune.autotune on every rank; rank 0 saves the choice."""
     import json
