@@ -48,6 +48,12 @@ void usage() {
       "  --seed S                seed for --init random\n"
       "  --out PATH|none         output file                            [per --naming]\n"
       "  --out-format dat|bin|checksum                                  [dat]\n"
+      "  --coarse FX[xFY]        after the run, also write a coarse view of the final state: one\n"
+      "                          value per FX x FY block of cells (FY = FX if omitted), reduced\n"
+      "                          on the device; needs --coarse-out (at most 2^22 coarse cells)\n"
+      "  --coarse-out PATH       its file: a grid of ceil(nx/FX) x ceil(ny/FY) values, text with\n"
+      "                          --out-format dat, else binary\n"
+      "  --coarse-stat mean|min|max  the value written per coarse cell            [mean]\n"
       "  --naming plain|mpi|cuda reference-style file names and messages [plain]\n"
       "  --dump-initial          also write the initial grid\n"
       "  --compat none|mpi|cuda  reference step-count/check semantics   [none]\n"
@@ -88,7 +94,28 @@ struct Options {
   int64_t ckpt_every = 0;
   int64_t warmup = 0;  // untimed steps first (graph capture, first touch), then the state is reset
   bool json = false, dump_initial = false;
+  // Coarse view of the final state (--coarse FX[xFY] --coarse-out PATH --coarse-stat S).
+  int64_t coarse_fx = 0, coarse_fy = 0;
+  std::string coarse_out, coarse_stat = "mean";
 };
+
+// "FX" or "FXxFY" -> the factors; false if malformed (a factor < 1 parses).
+bool parse_coarse(const std::string& s, int64_t* fx, int64_t* fy) {
+  char* end = nullptr;
+  if (s.empty()) return false;
+  const long long a = std::strtoll(s.c_str(), &end, 10);
+  if (end == s.c_str()) return false;
+  long long b = a;
+  if (*end == 'x' || *end == 'X') {
+    const char* q = end + 1;
+    b = std::strtoll(q, &end, 10);
+    if (end == q) return false;
+  }
+  if (*end != 0) return false;
+  *fx = a;
+  *fy = b;
+  return true;
+}
 
 // The live solvers of a single-process multi-rank run (heat --gpus N): a
 // failing rank aborts its peers' solvers (Solver::abort: ncclCommAbort, or
@@ -213,6 +240,42 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
     }
   }
   emit(final_path);
+  int64_t coarse_rows = 0, coarse_cols = 0;
+  if (o.coarse_fx > 0) {
+    // The chosen statistic of the final state as a CR x CC fp32 grid (the mean
+    // rounded once from fp64): prtdat text, or a binary grid whose header
+    // holds nx = CR, ny = CC and the step.
+    const Solver::CoarseView v = S.coarse(o.coarse_fx, o.coarse_fy);
+    coarse_rows = v.rows;
+    coarse_cols = v.cols;
+    if (root) {
+      std::vector<float> g(size_t(v.rows * v.cols));
+      for (int64_t i = 0; i < v.rows; ++i) {
+        const int64_t nr = std::min((i + 1) * o.coarse_fx, P.nx) - i * o.coarse_fx;
+        for (int64_t j = 0; j < v.cols; ++j) {
+          const int64_t nc = std::min((j + 1) * o.coarse_fy, P.ny) - j * o.coarse_fy;
+          const size_t k = size_t(i * v.cols + j);
+          g[k] = o.coarse_stat == "min"   ? v.min[k]
+                 : o.coarse_stat == "max" ? v.max[k]
+                                          : float(v.sum[k] / double(nr * nc));
+        }
+      }
+      if (o.out_format == "dat") {
+        write_dat(o.coarse_out, v.rows, v.cols, g.data());
+      } else {
+        BinHeader h{};
+        std::memcpy(h.magic, "HEATF32", 8);
+        h.version = 1;
+        h.nx = v.rows;
+        h.ny = v.cols;
+        h.step = S.step();
+        h.cx = P.cx;
+        h.cy = P.cy;
+        bin_create(o.coarse_out, h);
+        bin_write_block(o.coarse_out, v.rows, v.cols, 0, 0, v.rows, v.cols, g.data(), v.cols);
+      }
+    }
+  }
 
   if (root) {
     if (P.converge) {
@@ -244,7 +307,7 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
           "\"mcells_per_s\": %.3f, \"s_per_1000_iters\": %.6f, \"converged\": %s, "
           "\"converged_at\": %lld, \"last_resid\": %.6g, \"passes\": %lld, \"exchanges\": %lld, "
           "\"transport\": \"%s\", \"schedule\": \"%s\", \"halo\": %d, \"t_exchange\": %.6f, "
-          "\"t_compute\": %.6f, \"t_reduce\": %.6f, \"insulated\": \"%s\", \"periodic\": \"%s\"}\n",
+          "\"t_compute\": %.6f, \"t_reduce\": %.6f, \"insulated\": \"%s\", \"periodic\": \"%s\"",
           (long long)P.nx, (long long)P.ny, (long long)total, (long long)acc.steps_done, world,
           P.backend == Backend::Hip ? "hip" : "cpu", c.px, c.py, S.tb_depth(), secs,
           secs > 0 ? cells / secs / 1e6 : 0.0,
@@ -253,6 +316,18 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
           (long long)acc.passes, (long long)acc.exchanges, S.transport().name(),
           schedule_name(S.schedule()), S.halo(), acc.t_exchange, acc.t_compute, acc.t_reduce,
           insulated_name(P.insulated).c_str(), periodic_name(P.periodic).c_str());
+      if (o.coarse_fx > 0) {
+        std::string path;  // JSON string escapes
+        for (char ch : o.coarse_out) {
+          if (ch == '"' || ch == '\\') path += '\\';
+          path += ch;
+        }
+        std::printf(", \"coarse\": {\"fx\": %lld, \"fy\": %lld, \"rows\": %lld, \"cols\": %lld, "
+                    "\"stat\": \"%s\", \"path\": \"%s\"}",
+                    (long long)o.coarse_fx, (long long)o.coarse_fy, (long long)coarse_rows,
+                    (long long)coarse_cols, o.coarse_stat.c_str(), path.c_str());
+      }
+      std::printf("}\n");
     }
     std::fflush(stdout);
   }
@@ -268,6 +343,7 @@ int main(int argc, char** argv) {
   int gpus = 0;
   bool backend_set = false;
   bool plan = false;
+  bool coarse_set = false;
   int port = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -364,6 +440,28 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--coarse") {
+      const std::string s = need();
+      if (!parse_coarse(s, &o.coarse_fx, &o.coarse_fy)) {
+        std::fprintf(stderr, "heat: --coarse %s: expected FX or FXxFY (integer factors)\n",
+                     s.c_str());
+        return 2;
+      }
+      if (o.coarse_fx < 1 || o.coarse_fy < 1) {
+        std::fprintf(stderr, "heat: --coarse %s: a factor must be >= 1\n", s.c_str());
+        return 2;
+      }
+      coarse_set = true;
+    }
+    else if (a == "--coarse-out") o.coarse_out = need();
+    else if (a == "--coarse-stat") {
+      o.coarse_stat = need();
+      if (o.coarse_stat != "mean" && o.coarse_stat != "min" && o.coarse_stat != "max") {
+        std::fprintf(stderr, "heat: --coarse-stat %s: expected mean, min or max\n",
+                     o.coarse_stat.c_str());
+        return 2;
+      }
+    }
     else if (a == "--plan") plan = true;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 2; }
   }
@@ -371,6 +469,19 @@ int main(int argc, char** argv) {
     std::fprintf(stderr, "heat: axis %s is periodic (--periodic) and has an insulated side "
                  "(--insulated): choose one\n", axis);
     return 2;
+  }
+  if (coarse_set != !o.coarse_out.empty()) {
+    std::fprintf(stderr, "heat: --coarse and --coarse-out go together (%s is missing)\n",
+                 coarse_set ? "--coarse-out PATH" : "--coarse FX[xFY]");
+    return 2;
+  }
+  if (coarse_set) {
+    try {
+      coarse_dims(P.nx, P.ny, o.coarse_fx, o.coarse_fy, nullptr, nullptr);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "heat: --coarse: %s\n", e.what());
+      return 2;
+    }
   }
   if (o.naming == "mpi" && P.compat == Compat::None) P.compat = Compat::Mpi;
   if (o.naming == "cuda" && P.compat == Compat::None) P.compat = Compat::Cuda;

@@ -17,7 +17,7 @@
 extern "C" {
 #endif
 
-#define HEAT_ABI_VERSION 8
+#define HEAT_ABI_VERSION 9
 
 typedef struct heat_params {
   int64_t nx, ny;
@@ -154,6 +154,11 @@ int heat_solver_load_owned(heat_solver* s, const float* host, int64_t host_pitch
 /* rank 0: host must hold nx*ny floats; other ranks: host may be NULL */
 int heat_solver_gather(heat_solver* s, float* host);
 int heat_solver_checksum(heat_solver* s, heat_checksum* out);
+/* Coarse view of the current state: per fx x fy coarse cell the fp64 sum, the
+   min and the max, into host arrays of CR*CC (heat_coarse_dims) on every rank.
+   Collective; changes nothing of the run. */
+int heat_solver_coarse(heat_solver* s, int64_t fx, int64_t fy, double* sum, float* min,
+                       float* max);
 /* rank 0: full holds nx*ny floats (row-major); other ranks: full may be NULL */
 int heat_solver_scatter(heat_solver* s, const float* full, int64_t step);
 int heat_solver_write_bin(heat_solver* s, const char* path);
@@ -227,6 +232,42 @@ int heat_op_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly,
                      int64_t oy, int64_t ny, heat_checksum* out, void* stream);
 int heat_cpu_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
                       int64_t oy, int64_t ny, heat_checksum* out);
+/* Coarse view: CR = ceil(nx/fx), CC = ceil(ny/fy); fails on a factor < 1 or above
+   the limit of 2^22 coarse cells. */
+int heat_coarse_dims(int64_t nx, int64_t ny, int64_t fx, int64_t fy, int64_t* cr, int64_t* cc);
+/* MERGE the lx x ly block whose cell (0,0) is cell (ox, oy) of an nx x ny plate
+   into caller-owned CR*CC planes (initialised to 0, +inf, -inf; disjoint blocks
+   add up): the device kernel on device planes, enqueued on `stream` without
+   waiting, and its host twin on host memory. */
+int heat_op_coarse(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                   int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                   float* min, float* max, void* stream);
+int heat_cpu_coarse(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                    int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                    float* min, float* max);
+/* The launch plan heat_op_coarse takes for a block (heat::gpu::coarse_plan) with
+   the planner's constants, and a cap on the waves of a launch (0 = default) for
+   tests that want every loop of the kernel to run more than once. */
+typedef struct heat_coarse_plan {
+  int64_t strips, chunks, units;
+  int32_t owned, cells_per_strip, chunk_rows, cells_per_chunk, pieces, waves, vector_rows;
+  int32_t strip_cols, max_chunk_rows, min_chunk_rows, waves_per_cu; /* constants */
+  int32_t pad_;
+} heat_coarse_plan;
+int heat_op_coarse_plan(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                        int64_t oy, int64_t fx, int64_t fy, heat_coarse_plan* out);
+int heat_op_coarse_max_waves(int waves);
+/* Kernels alone, for timing (tools/coarse_bench.py): the merge into planes of
+   keys (heat::gpu::CoarsePlanes: sum, key(-min), key(max)), their reset, and the
+   checksum kernel accumulating into a caller-owned 32-byte device record.  No
+   allocation, copy or wait. */
+int heat_op_coarse_raw(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                       int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                       int32_t* nmin_key, int32_t* max_key, void* stream);
+int heat_op_coarse_reset(double* sum, int32_t* nmin_key, int32_t* max_key, int64_t cells,
+                         void* stream);
+int heat_op_checksum_raw(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                         int64_t oy, int64_t ny, void* record, void* stream);
 /* Mirror an lx x ly field into its `depth`-deep ghost frame beyond the insulated
    sides in `sides` (1 north, 2 south, 4 west, 8 east): the device kernel, and
    its host twin on host memory. */

@@ -64,4 +64,23 @@ struct Checksum {
 Checksum checksum_block(const float* src, int64_t src_pitch, int64_t ox, int64_t oy, int64_t lx,
                         int64_t ly, int64_t ny);
 
+// Coarse view of a field: integer factors fx (rows) and fy (columns) give the
+// CR x CC grid, CR = ceil(nx / fx), CC = ceil(ny / fy); coarse cell (I, J)
+// covers plate rows [I*fx, min((I+1)*fx, nx)) and columns
+// [J*fy, min((J+1)*fy, ny)).  The planes are all-reduced whole, so a view has
+// at most kCoarseMaxCells cells.
+constexpr int64_t kCoarseMaxCells = int64_t(1) << 22;
+// Throws (naming the limit and the factors) on a factor < 1 or a grid above
+// the limit.
+void coarse_dims(int64_t nx, int64_t ny, int64_t fx, int64_t fy, int64_t* cr, int64_t* cc);
+// MERGE the lx x ly block of host memory whose cell (0, 0) is plate cell
+// (ox, oy) into the CR x CC planes of the nx x ny plate: sum += the fp64 sum
+// of the cell's values, min / max the smaller / larger, a NaN in the cell
+// making all three NaN.  The caller initialises the planes (0, +inf, -inf);
+// several disjoint blocks may be merged into one set (host twin of
+// gpu::coarse_block).
+void coarse_block(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                  int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                  float* mn, float* mx);
+
 }  // namespace heat

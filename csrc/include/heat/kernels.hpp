@@ -293,6 +293,57 @@ void checksum_block(const float* origin, int64_t pitch, int64_t lx, int64_t ly, 
                     int64_t oy, int64_t ny, DeviceChecksum* out, hipStream_t st);
 float checksum_key_to_float(int key);
 
+// Coarse view of a field (coarse.hip): factors fx (rows) and fy (columns)
+// give the CR x CC grid of heat::coarse_dims; coarse cell (I, J) covers plate
+// rows [I*fx, min((I+1)*fx, nx)) and columns [J*fy, min((J+1)*fy, ny)).  Per
+// cell the planes hold the fp64 sum of its values (no fixed order) and its
+// min / max as order-preserving int keys, NaN on top, the min as the key of
+// the negated value so that both merge by an integer max (the residual
+// word's trick): a cell that holds a NaN reads NaN in all three.
+struct CoarsePlanes {
+  double* sum = nullptr;
+  int* nmin_key = nullptr;  // key(-min)
+  int* max_key = nullptr;
+};
+// Planes of `cells` cells to the identity (sum 0, min +inf, max -inf).
+void coarse_reset(const CoarsePlanes& p, int64_t cells, hipStream_t st);
+// In place, float planes (min, max) <-> keys.  Decoding with negated_min
+// leaves -min in the min plane (what an all-reduce by max wants).
+void coarse_encode(const CoarsePlanes& p, int64_t cells, hipStream_t st);
+void coarse_decode(const CoarsePlanes& p, int64_t cells, bool negated_min, hipStream_t st);
+// MERGE the lx x ly block whose cell (0, 0) is plate cell (ox, oy) at
+// `origin` into the planes of the nx x ny plate.  Blocks merged into one set
+// of planes must be disjoint: a coarse cell that lies whole inside one wave's
+// share of the block is written with plain stores, only cells cut by a
+// strip, a row chunk or the block's edge go through atomics (one per wave
+// and cell).  Reads owned cells only, never a ghost or padding cell.
+// Graph-capturable, no host synchronisation.
+void coarse_block(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                  int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy,
+                  const CoarsePlanes& planes, hipStream_t st);
+// The launch plan of coarse_block.  A unit is one wave's share: a strip of at
+// most kCoarseStripCols columns (whole coarse columns where fy allows:
+// `owned`) times a chunk of at most chunk_rows rows (whole coarse rows where
+// fx <= chunk_rows); the launch's waves grid-stride over the units.
+constexpr int kCoarseStripCols = 256;    // 64 lanes x float4
+constexpr int kCoarseMaxChunkRows = 64;  // halved down to kCoarseMinChunkRows
+constexpr int kCoarseMinChunkRows = 8;   // while the units do not fill the device
+constexpr int kCoarseWavesPerCu = 32;    // launch size: waves per CU
+struct CoarsePlan {
+  bool owned = false;        // strips hold whole coarse columns
+  int cells_per_strip = 0;   // owned: coarse columns per strip
+  int64_t strips = 0, chunks = 0, units = 0;
+  int chunk_rows = 0;        // rows per chunk (fx > chunk_rows: pieces of a coarse row)
+  int rows_per_chunk_cells = 0;  // fx <= chunk_rows: coarse rows per chunk, else 0
+  int pieces = 1;            // fx > chunk_rows: chunks per coarse row
+  int waves = 0;             // waves launched
+  bool vector_rows = false;  // rows read as aligned float4 (else scalar loads)
+};
+CoarsePlan coarse_plan(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                       int64_t oy, int64_t fx, int64_t fy);
+// Tests: cap the waves of a launch (0: kCoarseWavesPerCu per CU).
+void coarse_set_max_waves(int waves);
+
 // Device-side convergence decision (one per check, stream-ordered after the
 // residual of the check's pass and its all-reduce): the host never waits on a
 // check.  Unless the gate is already closed, judge_check compares the

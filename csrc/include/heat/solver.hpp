@@ -142,6 +142,16 @@ class Solver {
   void scatter_root(const float* full, int64_t step);
   // Global order-independent checksum (identical on every rank).
   Checksum checksum();
+  // Coarse view of the current state (io.hpp: coarse_dims / coarse_block):
+  // the fp64 sum, min and max of every fx x fy coarse cell of the plate,
+  // reduced on the device, identical on every rank.  Collective.  Leaves the
+  // state, the ghost depth, the step count and every captured graph alone.
+  struct CoarseView {
+    int64_t rows = 0, cols = 0;
+    std::vector<double> sum;
+    std::vector<float> min, max;
+  };
+  CoarseView coarse(int64_t fx, int64_t fy);
   // Binary output / checkpoint of the current state (all ranks call).
   void write_bin(const std::string& path);
   void read_bin(const std::string& path);
@@ -326,6 +336,8 @@ class Solver {
   float* h_resid_ = nullptr;
   void* d_scratch_ = nullptr;
   void* d_checksum_ = nullptr;
+  void* d_coarse_ = nullptr;  // planes of coarse(): 16 bytes per coarse cell, grown on demand
+  int64_t coarse_cells_ = 0;
   struct GraphEntry {
     hipGraphExec_t exec = nullptr;
     int cur_after = 0;

@@ -431,6 +431,17 @@ int heat_solver_checksum(heat_solver* s, heat_checksum* out) {
   });
 }
 
+int heat_solver_coarse(heat_solver* s, int64_t fx, int64_t fy, double* sum, float* min,
+                       float* max) {
+  return guard([&] {
+    HEAT_CHECK(sum && min && max, "null coarse planes");
+    const heat::Solver::CoarseView v = s->s->coarse(fx, fy);
+    std::memcpy(sum, v.sum.data(), v.sum.size() * 8);
+    std::memcpy(min, v.min.data(), v.min.size() * 4);
+    std::memcpy(max, v.max.data(), v.max.size() * 4);
+  });
+}
+
 int heat_solver_scatter(heat_solver* s, const float* full, int64_t step) {
   return guard([&] { s->s->scatter_root(full, step); });
 }
@@ -662,6 +673,98 @@ int heat_cpu_checksum(const float* origin, int64_t pitch, int64_t lx, int64_t ly
     out->min = c.min;
     out->max = c.max;
     out->count = c.count;
+  });
+}
+
+int heat_coarse_dims(int64_t nx, int64_t ny, int64_t fx, int64_t fy, int64_t* cr, int64_t* cc) {
+  return guard([&] { heat::coarse_dims(nx, ny, fx, fy, cr, cc); });
+}
+
+int heat_op_coarse(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                   int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                   float* min, float* max, void* stream) {
+  return guard([&] {
+    HEAT_CHECK(sum && min && max, "null coarse planes");
+    int64_t cr = 0, cc = 0;
+    heat::coarse_dims(nx, ny, fx, fy, &cr, &cc);
+    // The caller's float planes become keys for the merge and floats again.
+    heat::gpu::CoarsePlanes pl;
+    pl.sum = sum;
+    pl.nmin_key = reinterpret_cast<int*>(min);
+    pl.max_key = reinterpret_cast<int*>(max);
+    heat::gpu::coarse_encode(pl, cr * cc, S(stream));
+    heat::gpu::coarse_block(origin, pitch, lx, ly, ox, oy, nx, ny, fx, fy, pl, S(stream));
+    heat::gpu::coarse_decode(pl, cr * cc, false, S(stream));
+  });
+}
+
+int heat_cpu_coarse(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                    int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                    float* min, float* max) {
+  return guard([&] {
+    HEAT_CHECK(sum && min && max, "null coarse planes");
+    heat::coarse_dims(nx, ny, fx, fy, nullptr, nullptr);
+    heat::coarse_block(origin, pitch, lx, ly, ox, oy, nx, ny, fx, fy, sum, min, max);
+  });
+}
+
+int heat_op_coarse_plan(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                        int64_t oy, int64_t fx, int64_t fy, heat_coarse_plan* out) {
+  return guard([&] {
+    const heat::gpu::CoarsePlan p = heat::gpu::coarse_plan(origin, pitch, lx, ly, ox, oy, fx, fy);
+    std::memset(out, 0, sizeof *out);
+    out->strips = p.strips;
+    out->chunks = p.chunks;
+    out->units = p.units;
+    out->owned = p.owned;
+    out->cells_per_strip = p.cells_per_strip;
+    out->chunk_rows = p.chunk_rows;
+    out->cells_per_chunk = p.rows_per_chunk_cells;
+    out->pieces = p.pieces;
+    out->waves = p.waves;
+    out->vector_rows = p.vector_rows;
+    out->strip_cols = heat::gpu::kCoarseStripCols;
+    out->max_chunk_rows = heat::gpu::kCoarseMaxChunkRows;
+    out->min_chunk_rows = heat::gpu::kCoarseMinChunkRows;
+    out->waves_per_cu = heat::gpu::kCoarseWavesPerCu;
+  });
+}
+
+int heat_op_coarse_max_waves(int waves) {
+  return guard([&] { heat::gpu::coarse_set_max_waves(waves); });
+}
+
+int heat_op_coarse_raw(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                       int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                       int32_t* nmin_key, int32_t* max_key, void* stream) {
+  return guard([&] {
+    // The kernel itself has no limit on the coarse grid (the front ends' 2^22
+    // cells bound what is all-reduced and copied): 2x2 on 8192^2 is timed here.
+    heat::gpu::CoarsePlanes pl;
+    pl.sum = sum;
+    pl.nmin_key = nmin_key;
+    pl.max_key = max_key;
+    heat::gpu::coarse_block(origin, pitch, lx, ly, ox, oy, nx, ny, fx, fy, pl, S(stream));
+  });
+}
+
+int heat_op_coarse_reset(double* sum, int32_t* nmin_key, int32_t* max_key, int64_t cells,
+                         void* stream) {
+  return guard([&] {
+    heat::gpu::CoarsePlanes pl;
+    pl.sum = sum;
+    pl.nmin_key = nmin_key;
+    pl.max_key = max_key;
+    heat::gpu::coarse_reset(pl, cells, S(stream));
+  });
+}
+
+int heat_op_checksum_raw(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                         int64_t oy, int64_t ny, void* record, void* stream) {
+  return guard([&] {
+    HEAT_CHECK(record != nullptr, "null checksum record");
+    heat::gpu::checksum_block(origin, pitch, lx, ly, ox, oy, ny,
+                              static_cast<heat::gpu::DeviceChecksum*>(record), S(stream));
   });
 }
 

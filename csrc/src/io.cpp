@@ -4,6 +4,7 @@
 #include <fcntl.h>
 #include <unistd.h>
 
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
@@ -202,6 +203,58 @@ Checksum checksum_block(const float* src, int64_t src_pitch, int64_t ox, int64_t
   }
   c.count = lx * ly;
   return c;
+}
+
+void coarse_dims(int64_t nx, int64_t ny, int64_t fx, int64_t fy, int64_t* cr, int64_t* cc) {
+  HEAT_CHECK(nx >= 1 && ny >= 1, "coarse view of a %lldx%lld plate", (long long)nx, (long long)ny);
+  HEAT_CHECK(fx >= 1 && fy >= 1, "coarse factors %lldx%lld: a factor must be >= 1", (long long)fx,
+             (long long)fy);
+  const int64_t r = ceil_div(nx, fx), c = ceil_div(ny, fy);
+  HEAT_CHECK(r <= kCoarseMaxCells && c <= kCoarseMaxCells && r * c <= kCoarseMaxCells,
+             "coarse factors %lldx%lld give a %lldx%lld grid of a %lldx%lld plate: above the "
+             "limit of %lld coarse cells (2^22)",
+             (long long)fx, (long long)fy, (long long)r, (long long)c, (long long)nx, (long long)ny,
+             (long long)kCoarseMaxCells);
+  if (cr) *cr = r;
+  if (cc) *cc = c;
+}
+
+void coarse_block(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
+                  int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
+                  float* mn, float* mx) {
+  if (lx <= 0 || ly <= 0) return;
+  HEAT_CHECK(fx >= 1 && fy >= 1 && ox >= 0 && oy >= 0 && ox + lx <= nx && oy + ly <= ny,
+             "coarse of a %lldx%lld block at (%lld, %lld) of a %lldx%lld plate, factors %lldx%lld",
+             (long long)lx, (long long)ly, (long long)ox, (long long)oy, (long long)nx,
+             (long long)ny, (long long)fx, (long long)fy);
+  const int64_t cc = ceil_div(ny, fy);
+  const float nan = std::numeric_limits<float>::quiet_NaN();
+  // Coarse row by coarse row, each column segment of a cell row by row.
+  for (int64_t g = ox; g < ox + lx;) {
+    const int64_t I = g / fx, g1 = std::min(ox + lx, fx > nx ? nx : (I + 1) * fx);
+    for (int64_t h = oy; h < oy + ly;) {
+      const int64_t J = h / fy, h1 = std::min(oy + ly, fy > ny ? ny : (J + 1) * fy);
+      double s = 0.0;
+      float lo = std::numeric_limits<float>::infinity(), hi = -lo;
+      bool has_nan = false;
+      for (int64_t r = g; r < g1; ++r) {
+        const float* row = origin + (r - ox) * pitch;
+        for (int64_t c = h; c < h1; ++c) {
+          const float v = row[c - oy];
+          s += double(v);
+          lo = std::min(lo, v);
+          hi = std::max(hi, v);
+          has_nan |= v != v;
+        }
+      }
+      const int64_t k = I * cc + J;
+      sum[k] += s;
+      mn[k] = (has_nan || mn[k] != mn[k]) ? nan : std::min(mn[k], lo);
+      mx[k] = (has_nan || mx[k] != mx[k]) ? nan : std::max(mx[k], hi);
+      h = h1;
+    }
+    g = g1;
+  }
 }
 
 }  // namespace heat

@@ -7,6 +7,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <thread>
 
@@ -348,6 +349,7 @@ void Solver::free_all() {
     if (h_resid_) (void)hipHostFree(h_resid_);
     if (d_scratch_) (void)hipFree(d_scratch_);
     if (d_checksum_) (void)hipFree(d_checksum_);
+    if (d_coarse_) (void)hipFree(d_coarse_);
     if (d_gate_) (void)hipFree(d_gate_);
     for (auto& b : xbase_)
       if (b) (void)hipFree(b);
@@ -372,6 +374,8 @@ void Solver::free_all() {
   d_resid_ = nullptr;
   h_resid_ = nullptr;
   d_scratch_ = d_checksum_ = nullptr;
+  d_coarse_ = nullptr;
+  coarse_cells_ = 0;
   d_gate_ = h_gate_ = nullptr;
   xbase_[0] = xbase_[1] = nullptr;
   d_flags_ = nullptr;
@@ -1961,6 +1965,62 @@ Checksum Solver::checksum() {
   g.max = m[0];
   g.min = -m[1];
   return g;
+}
+
+Solver::CoarseView Solver::coarse(int64_t fx, int64_t fy) {
+  complete_pending();
+  TraceRange tr("heat.coarse");
+  CoarseView v;
+  coarse_dims(P_.nx, P_.ny, fx, fy, &v.rows, &v.cols);
+  const int64_t n = v.rows * v.cols;
+  v.sum.assign(size_t(n), 0.0);
+  // The min plane travels negated (an all-reduce by max), like the checksum's.
+  v.min.assign(size_t(n), -std::numeric_limits<float>::infinity());
+  v.max.assign(size_t(n), -std::numeric_limits<float>::infinity());
+  const bool peers = tr_->world() > 1;
+  if (on_gpu()) {
+    if (n > coarse_cells_) {
+      if (d_coarse_) HIP_CHECK(hipFree(d_coarse_));
+      d_coarse_ = nullptr;
+      coarse_cells_ = 0;
+      HIP_CHECK(hipMalloc(&d_coarse_, size_t(n) * 16));
+      coarse_cells_ = n;
+    }
+    gpu::CoarsePlanes pl;
+    pl.sum = static_cast<double*>(d_coarse_);
+    pl.nmin_key = reinterpret_cast<int*>(pl.sum + n);
+    pl.max_key = pl.nmin_key + n;
+    gpu::coarse_reset(pl, n, s_comp_);
+    gpu::coarse_block(field_[cur_], L_.pitch, blk_.lx, blk_.ly, blk_.ox, blk_.oy, P_.nx, P_.ny, fx,
+                      fy, pl, s_comp_);
+    gpu::coarse_decode(pl, n, /*negated_min=*/true, s_comp_);
+    if (peers && tr_->device_memory()) {
+      tr_->allreduce_sum_f64(pl.sum, int(n), s_comp_);
+      tr_->allreduce_max(reinterpret_cast<float*>(pl.nmin_key), int(n), s_comp_);
+      tr_->allreduce_max(reinterpret_cast<float*>(pl.max_key), int(n), s_comp_);
+    }
+    HIP_CHECK(hipMemcpyAsync(v.sum.data(), pl.sum, size_t(n) * 8, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(
+        hipMemcpyAsync(v.min.data(), pl.nmin_key, size_t(n) * 4, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(
+        hipMemcpyAsync(v.max.data(), pl.max_key, size_t(n) * 4, hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+  } else {
+    std::vector<float> mine(static_cast<size_t>(blk_.lx * blk_.ly));
+    copy_owned(mine.data(), blk_.ly);
+    std::vector<float> lo(size_t(n), std::numeric_limits<float>::infinity());
+    coarse_block(mine.data(), blk_.ly, blk_.lx, blk_.ly, blk_.ox, blk_.oy, P_.nx, P_.ny, fx, fy,
+                 v.sum.data(), lo.data(), v.max.data());
+    for (int64_t i = 0; i < n; ++i) v.min[size_t(i)] = -lo[size_t(i)];
+  }
+  if (peers && !(on_gpu() && tr_->device_memory())) {
+    // Host-memory transport (CPU ranks, ranks sharing a GPU): reduced on the host.
+    tr_->allreduce_sum_f64(v.sum.data(), int(n), nullptr);
+    tr_->allreduce_max(v.min.data(), int(n), nullptr);
+    tr_->allreduce_max(v.max.data(), int(n), nullptr);
+  }
+  for (auto& m : v.min) m = -m;
+  return v;
 }
 
 void Solver::write_bin(const std::string& path) {

@@ -22,7 +22,7 @@ from pathlib import Path
 
 import torch  # noqa: F401  (must be imported before libheat: shared HIP runtime)
 
-ABI_VERSION = 8  # must match HEAT_ABI_VERSION in csrc/include/heat/capi.h
+ABI_VERSION = 9  # must match HEAT_ABI_VERSION in csrc/include/heat/capi.h
 
 PKG_DIR = Path(__file__).resolve().parent
 REPO_DIR = PKG_DIR.parent
@@ -114,6 +114,14 @@ class HeatTbTuning(Structure):
                 ("tile_xl", c_int32), ("nt", c_int32), ("pad_", c_int32)]
 
 
+class HeatCoarsePlan(Structure):
+    _fields_ = [("strips", c_int64), ("chunks", c_int64), ("units", c_int64),
+                ("owned", c_int32), ("cells_per_strip", c_int32), ("chunk_rows", c_int32),
+                ("cells_per_chunk", c_int32), ("pieces", c_int32), ("waves", c_int32),
+                ("vector_rows", c_int32), ("strip_cols", c_int32), ("max_chunk_rows", c_int32),
+                ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32), ("pad_", c_int32)]
+
+
 class HeatChecksum(Structure):
     _fields_ = [("hash", c_uint64), ("sum", c_double), ("min", c_double), ("max", c_double),
                 ("count", c_int64)]
@@ -190,6 +198,16 @@ _SIGS = {
                                  POINTER(HeatChecksum), c_void_p]),
     "heat_cpu_checksum": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int64, c_int64, c_int64,
                                   POINTER(HeatChecksum)]),
+    "heat_solver_coarse": (c_int, [c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_void_p]),
+    "heat_coarse_dims": (c_int, [c_int64, c_int64, c_int64, c_int64, POINTER(c_int64),
+                                 POINTER(c_int64)]),
+    "heat_op_coarse": (c_int, [c_void_p] + [c_int64] * 9 + [c_void_p] * 4),
+    "heat_cpu_coarse": (c_int, [c_void_p] + [c_int64] * 9 + [c_void_p] * 3),
+    "heat_op_coarse_plan": (c_int, [c_void_p] + [c_int64] * 7 + [POINTER(HeatCoarsePlan)]),
+    "heat_op_coarse_max_waves": (c_int, [c_int]),
+    "heat_op_coarse_raw": (c_int, [c_void_p] + [c_int64] * 9 + [c_void_p] * 4),
+    "heat_op_coarse_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
+    "heat_op_checksum_raw": (c_int, [c_void_p] + [c_int64] * 6 + [c_void_p, c_void_p]),
     "heat_op_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
                                               c_void_p]),
     "heat_cpu_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int,
@@ -331,6 +349,7 @@ def rccl_unique_id() -> bytes:
 
 __all__ = [
     "HeatParams", "HeatComm", "HeatMsg", "HeatTransportInfo", "HeatTbTuning", "HeatRunStats", "HeatBlockInfo", "HeatChecksum",
+    "HeatCoarsePlan",
     "SENDRECV_CB", "ALLREDUCE_CB", "BARRIER_CB", "NativeError", "lib", "call", "check",
     "available", "build_native", "loaded_path", "device_count", "rccl_unique_id",
     "require_gpu_native", "LIB_PATH", "CLI_PATH", "c_uint", "EXP_PATH", "load_exp", "unload_exp",

@@ -50,6 +50,15 @@ def build_parser() -> argparse.ArgumentParser:
     a("--seed", type=int, default=0)
     a("--out", default=None)
     a("--out-format", choices=["dat", "bin", "checksum"], default="dat")
+    a("--coarse", default=None, metavar="FX[xFY]",
+      help="after the run, also write a coarse view of the final state: one value per FX x FY "
+           "block of cells (FY = FX if omitted), reduced on the device; needs --coarse-out "
+           "(at most 2^22 coarse cells)")
+    a("--coarse-out", default=None, metavar="PATH",
+      help="its file: a grid of ceil(nx/FX) x ceil(ny/FY) values, text with --out-format dat, "
+           "else binary")
+    a("--coarse-stat", choices=["mean", "min", "max"], default="mean",
+      help="the value written per coarse cell")
     a("--naming", choices=["plain", "mpi", "cuda"], default="plain")
     a("--dump-initial", action="store_true")
     a("--compat", choices=["none", "mpi", "cuda"], default=None)
@@ -84,6 +93,21 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
+def parse_coarse(text: str):
+    """"FX" or "FXxFY" -> (fx, fy); ValueError if malformed or a factor < 1."""
+    parts = text.lower().split("x")
+    try:
+        f = [int(p) for p in parts]
+    except ValueError:
+        f = []
+    if len(f) not in (1, 2):
+        raise ValueError(f"--coarse {text}: expected FX or FXxFY (integer factors)")
+    fx, fy = f[0], f[-1]
+    if fx < 1 or fy < 1:
+        raise ValueError(f"--coarse {text}: a factor must be >= 1")
+    return fx, fy
+
+
 def main(argv=None) -> int:
     argv = list(sys.argv[1:] if argv is None else argv)
     parser = build_parser()
@@ -93,6 +117,17 @@ def main(argv=None) -> int:
         check_edges(args.insulated, args.periodic)
     except ValueError as e:
         parser.error(str(e))
+    coarse = None
+    if (args.coarse is None) != (args.coarse_out is None):
+        missing = "--coarse-out PATH" if args.coarse_out is None else "--coarse FX[xFY]"
+        parser.error(f"--coarse and --coarse-out go together ({missing} is missing)")
+    if args.coarse is not None:
+        try:
+            coarse = parse_coarse(args.coarse)
+            from .ops import coarse_dims
+            coarse_dims(args.nx, args.ny, *coarse)
+        except (ValueError, _native.NativeError) as e:
+            parser.error(f"--coarse: {e}" if not str(e).startswith("--coarse") else str(e))
     if args.gpus > 0 or args.plan:
         # Single-process native modes: the `heat` binary owns the threads
         # and the planner; same flags, same output.
@@ -178,6 +213,21 @@ def main(argv=None) -> int:
             converged, converged_at = True, r.converged_at
             break
     emit(final_path)
+    coarse_info = None
+    if coarse is not None:
+        # The chosen statistic of the final state as a CR x CC fp32 grid (the
+        # mean rounded once from fp64): prtdat text, or a binary grid whose
+        # header holds nx = CR, ny = CC and the step.
+        v = solver.coarse(*coarse)
+        g = v[args.coarse_stat].astype("float32")
+        if root:
+            if args.out_format == "dat":
+                hio.write_dat(args.coarse_out, g)
+            else:
+                hio.write_bin(args.coarse_out, g, step=solver.step, cx=cfg.cx, cy=cfg.cy)
+        coarse_info = {"fx": coarse[0], "fy": coarse[1], "rows": int(g.shape[0]),
+                       "cols": int(g.shape[1]), "stat": args.coarse_stat,
+                       "path": args.coarse_out}
     if root:
         if cfg.converge:
             out.write(report.convergence_line(args.naming, converged, converged_at, solver.step))
@@ -197,7 +247,8 @@ def main(argv=None) -> int:
                 halo=solver.info.halo, t_exchange=acc["t_exchange"],
                 t_compute=acc["t_compute"], t_reduce=acc["t_reduce"],
                 insulated=solver.info.insulated, periodic=solver.info.periodic,
-                native=_native.loaded_path()) + "\n")
+                native=_native.loaded_path(),
+                **({"coarse": coarse_info} if coarse_info else {})) + "\n")
         out.flush()
     solver.barrier()
     solver.close()

@@ -262,6 +262,35 @@ class HeatSolver:
         return {"hash": f"{c.hash:016x}", "sum": c.sum, "min": c.min, "max": c.max,
                 "count": c.count}
 
+    def coarse(self, fx: int, fy: Optional[int] = None) -> dict:
+        """Coarse view of the current state, reduced where the field lives (no
+        rank ever holds the grid): coarse cell (I, J) covers plate rows
+        [I*fx, (I+1)*fx) and columns [J*fy, (J+1)*fy), cut at the plate's edge
+        (fy defaults to fx).  Returns NumPy arrays of shape (ceil(nx/fx),
+        ceil(ny/fy)): "sum" (float64, no fixed order), "min", "max" (float32),
+        "count" (int64 cells per coarse cell) and "mean" = sum / count
+        (float64); a coarse cell that holds a NaN is NaN in all of them.
+        Identical on every rank.  Collective; the run continues as if it had
+        not been called."""
+        fx = int(fx)
+        fy = fx if fy is None else int(fy)
+        cr, cc = ctypes.c_int64(0), ctypes.c_int64(0)
+        _native.call("heat_coarse_dims", self.config.nx, self.config.ny, fx, fy,
+                     ctypes.byref(cr), ctypes.byref(cc))
+        shape = (int(cr.value), int(cc.value))
+        s = np.empty(shape, np.float64)
+        mn = np.empty(shape, np.float32)
+        mx = np.empty(shape, np.float32)
+        _native.call("heat_solver_coarse", self._h, fx, fy, s.ctypes.data, mn.ctypes.data,
+                     mx.ctypes.data)
+        r0 = np.arange(0, self.config.nx, fx, dtype=np.int64)
+        c0 = np.arange(0, self.config.ny, fy, dtype=np.int64)
+        count = ((np.minimum(r0 + fx, self.config.nx) - r0)[:, None]
+                 * (np.minimum(c0 + fy, self.config.ny) - c0)[None, :])
+        with np.errstate(invalid="ignore"):
+            mean = s / count
+        return {"mean": mean, "sum": s, "min": mn, "max": mx, "count": count}
+
     def save(self, path: str) -> None:
         """Binary grid / checkpoint (header + nx*ny fp32); collective."""
         _native.call("heat_solver_write_bin", self._h, str(path).encode())

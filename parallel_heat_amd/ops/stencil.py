@@ -359,6 +359,72 @@ def checksum(f: Field, ox: int = 0, oy: int = 0, ny: Optional[int] = None) -> di
     return {"hash": int(c.hash), "sum": c.sum, "min": c.min, "max": c.max, "count": int(c.count)}
 
 
+def coarse_dims(nx: int, ny: int, fx: int, fy: int) -> Tuple[int, int]:
+    """Rows and columns (ceil(nx / fx), ceil(ny / fy)) of the coarse view of an
+    nx x ny plate; raises on a factor < 1 or above the limit of 2**22 cells."""
+    cr, cc = ctypes.c_int64(0), ctypes.c_int64(0)
+    _native.call("heat_coarse_dims", int(nx), int(ny), int(fx), int(fy), ctypes.byref(cr),
+                 ctypes.byref(cc))
+    return int(cr.value), int(cc.value)
+
+
+def coarse(f: Field, fx: int, fy: int, ox: int = 0, oy: int = 0, nx: Optional[int] = None,
+           ny: Optional[int] = None, out: Optional[dict] = None) -> dict:
+    """Coarse view of the field's owned block placed at (ox, oy) of an nx x ny
+    plate (default: the block is the plate): coarse cell (I, J) covers plate
+    rows [I*fx, (I+1)*fx) and columns [J*fy, (J+1)*fy), cut at the plate's edge.
+    Returns {"sum": float64, "min", "max": float32} tensors of shape
+    (ceil(nx/fx), ceil(ny/fy)) on the field's device and "count" (int64, the
+    geometric cell counts).  A cell that holds a NaN is NaN in all three.
+    `out`: the dict of an earlier call, into which this (disjoint) block is
+    merged.  The device kernel on a GPU field (enqueued on the current stream),
+    the host heat::coarse_block on a CPU field."""
+    nx = f.lx if nx is None else int(nx)
+    ny = f.ly if ny is None else int(ny)
+    fx, fy = int(fx), int(fy)
+    cr, cc = coarse_dims(nx, ny, fx, fy)
+    if out is None:
+        dev = f.device
+        out = {"sum": torch.zeros((cr, cc), dtype=torch.float64, device=dev),
+               "min": torch.full((cr, cc), float("inf"), dtype=torch.float32, device=dev),
+               "max": torch.full((cr, cc), float("-inf"), dtype=torch.float32, device=dev)}
+    for k, dt in (("sum", torch.float64), ("min", torch.float32), ("max", torch.float32)):
+        t = out[k]
+        if (t.dtype != dt or tuple(t.shape) != (cr, cc) or not t.is_contiguous()
+                or t.device != f.device):
+            raise ValueError(f"out[{k!r}] must be a contiguous {dt} ({cr}, {cc}) tensor on "
+                             f"{f.device}")
+    args = (ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly, int(ox), int(oy), nx, ny, fx, fy,
+            ctypes.c_void_p(out["sum"].data_ptr()), ctypes.c_void_p(out["min"].data_ptr()),
+            ctypes.c_void_p(out["max"].data_ptr()))
+    if f.device.type == "cpu":
+        _native.call("heat_cpu_coarse", *args)
+    else:
+        _native.call("heat_op_coarse", *args, ctypes.c_void_p(_stream()))
+    rows = torch.clamp(torch.arange(1, cr + 1, dtype=torch.int64) * fx, max=nx) - \
+        torch.arange(cr, dtype=torch.int64) * fx
+    cols = torch.clamp(torch.arange(1, cc + 1, dtype=torch.int64) * fy, max=ny) - \
+        torch.arange(cc, dtype=torch.int64) * fy
+    out["count"] = rows[:, None] * cols[None, :]
+    return out
+
+
+def coarse_plan(f: Field, fx: int, fy: int, ox: int = 0, oy: int = 0) -> dict:
+    """The launch plan `coarse` takes for this GPU field (strips, chunks, units,
+    waves, ...) together with the planner's constants strip_cols,
+    max_chunk_rows, min_chunk_rows and waves_per_cu."""
+    p = _native.HeatCoarsePlan()
+    _native.call("heat_op_coarse_plan", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly, int(ox),
+                 int(oy), int(fx), int(fy), ctypes.byref(p))
+    return {k: int(getattr(p, k)) for k, _ in p._fields_ if k != "pad_"}
+
+
+def set_coarse_max_waves(waves: int) -> None:
+    """Cap the waves of a `coarse` launch (0: the default, from the CU count):
+    tests make the kernel's grid-stride loop run more than once with it."""
+    _native.call("heat_op_coarse_max_waves", int(waves))
+
+
 def fill_insulated_ghosts(f: Field, sides: str, depth: int) -> None:
     """Insulated (zero-flux) plate edges: fill the field's ghost frame, `depth`
     cells deep, beyond every side in `sides` (letters of "nswe", or "all")
