@@ -118,6 +118,22 @@ selftest-asan: $(BUILD)/selftest-asan
 	ASAN_OPTIONS=detect_leaks=1 $(BUILD)/selftest-asan
 .PHONY: selftest selftest-asan
 
+# The same for the refinement (refine_axis and the host twin refine_block).
+REFINE_SELFTEST_SRCS := csrc/tests/refine_selftest.cpp csrc/src/common.cpp csrc/src/io.cpp
+$(BUILD)/refine-selftest: $(REFINE_SELFTEST_SRCS) $(HDRS)
+	@mkdir -p $(BUILD)
+	g++ -std=c++17 -O2 -g -Wall -Icsrc/include -mfma -mavx2 $(REFINE_SELFTEST_SRCS) -o $@
+$(BUILD)/refine-selftest-asan: $(REFINE_SELFTEST_SRCS) $(HDRS)
+	@mkdir -p $(BUILD)
+	g++ -std=c++17 -O1 -g -Wall -Icsrc/include -mfma -mavx2 \
+	  -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
+	  $(REFINE_SELFTEST_SRCS) -o $@
+refine-selftest: $(BUILD)/refine-selftest
+	$(BUILD)/refine-selftest
+refine-selftest-asan: $(BUILD)/refine-selftest-asan
+	ASAN_OPTIONS=detect_leaks=1 $(BUILD)/refine-selftest-asan
+.PHONY: refine-selftest refine-selftest-asan
+
 # Reference-compatible program names (mpi/Makefile:12-22, cuda/Makefile:13):
 #   make ref-variants SIZE=900 STEPS=10000 STEP=20 THREADS=4
 # writes build/ref/{heat_N,heat_omp_N,heat_con_N,heat_con_omp_N,cuda_heat}; run

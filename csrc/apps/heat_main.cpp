@@ -54,6 +54,12 @@ void usage() {
       "  --coarse-out PATH       its file: a grid of ceil(nx/FX) x ceil(ny/FY) values, text with\n"
       "                          --out-format dat, else binary\n"
       "  --coarse-stat mean|min|max  the value written per coarse cell            [mean]\n"
+      "  --init-from PATH        start from a coarse grid: a binary grid file (what --coarse-out\n"
+      "                          writes) refined onto the plate on the device; overrides --init,\n"
+      "                          the run starts at step 0; not with --resume\n"
+      "  --refine FX[xFY]        its integer factors (FY = FX if omitted); the file must hold\n"
+      "                          ceil(nx/FX) x ceil(ny/FY) values  [ceil(nx/rows) x ceil(ny/cols)]\n"
+      "  --refine-order 0|1      piecewise constant, or cell-centred bilinear            [1]\n"
       "  --naming plain|mpi|cuda reference-style file names and messages [plain]\n"
       "  --dump-initial          also write the initial grid\n"
       "  --compat none|mpi|cuda  reference step-count/check semantics   [none]\n"
@@ -97,6 +103,11 @@ struct Options {
   // Coarse view of the final state (--coarse FX[xFY] --coarse-out PATH --coarse-stat S).
   int64_t coarse_fx = 0, coarse_fy = 0;
   std::string coarse_out, coarse_stat = "mean";
+  // Start from a coarse grid (--init-from PATH --refine FX[xFY] --refine-order K).
+  std::string init_from;
+  int64_t refine_fx = 0, refine_fy = 0, src_rows = 0, src_cols = 0;
+  int refine_order = 1;
+  std::vector<float> src;  // the file's grid, read once in main
 };
 
 // "FX" or "FXxFY" -> the factors; false if malformed (a factor < 1 parses).
@@ -165,6 +176,11 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
   } registered{reg, rank};
   if (reg) reg->set(rank, &S);
   if (!o.resume.empty()) S.read_bin(o.resume);
+  auto start = [&] {
+    if (!o.init_from.empty())
+      S.refine(o.src.data(), o.src_rows, o.src_cols, o.refine_fx, o.refine_fy, o.refine_order, 0);
+  };
+  start();
 
   const bool small = P.nx * P.ny <= (int64_t(1) << 24);
   std::string init_path, final_path;
@@ -213,6 +229,7 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
     HEAT_CHECK(o.resume.empty(), "--warmup with --resume");
     (void)S.run(o.warmup);
     S.reset();
+    start();
   }
   if (o.dump_initial || o.naming == "mpi") emit(init_path);
 
@@ -327,6 +344,17 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
                     (long long)o.coarse_fx, (long long)o.coarse_fy, (long long)coarse_rows,
                     (long long)coarse_cols, o.coarse_stat.c_str(), path.c_str());
       }
+      if (!o.init_from.empty()) {
+        std::string path;  // JSON string escapes
+        for (char ch : o.init_from) {
+          if (ch == '"' || ch == '\\') path += '\\';
+          path += ch;
+        }
+        std::printf(", \"init_from\": {\"path\": \"%s\", \"rows\": %lld, \"cols\": %lld, "
+                    "\"fx\": %lld, \"fy\": %lld, \"order\": %d}",
+                    path.c_str(), (long long)o.src_rows, (long long)o.src_cols,
+                    (long long)o.refine_fx, (long long)o.refine_fy, o.refine_order);
+      }
       std::printf("}\n");
     }
     std::fflush(stdout);
@@ -344,6 +372,7 @@ int main(int argc, char** argv) {
   bool backend_set = false;
   bool plan = false;
   bool coarse_set = false;
+  bool refine_set = false;
   int port = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -462,6 +491,28 @@ int main(int argc, char** argv) {
         return 2;
       }
     }
+    else if (a == "--init-from") o.init_from = need();
+    else if (a == "--refine") {
+      const std::string s = need();
+      if (!parse_coarse(s, &o.refine_fx, &o.refine_fy)) {
+        std::fprintf(stderr, "heat: --refine %s: expected FX or FXxFY (integer factors)\n",
+                     s.c_str());
+        return 2;
+      }
+      if (o.refine_fx < 1 || o.refine_fy < 1) {
+        std::fprintf(stderr, "heat: --refine %s: a factor must be >= 1\n", s.c_str());
+        return 2;
+      }
+      refine_set = true;
+    }
+    else if (a == "--refine-order") {
+      const std::string s = need();
+      if (s != "0" && s != "1") {
+        std::fprintf(stderr, "heat: --refine-order %s: expected 0 or 1\n", s.c_str());
+        return 2;
+      }
+      o.refine_order = s == "1";
+    }
     else if (a == "--plan") plan = true;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 2; }
   }
@@ -480,6 +531,36 @@ int main(int argc, char** argv) {
       coarse_dims(P.nx, P.ny, o.coarse_fx, o.coarse_fy, nullptr, nullptr);
     } catch (const std::exception& e) {
       std::fprintf(stderr, "heat: --coarse: %s\n", e.what());
+      return 2;
+    }
+  }
+  if (o.init_from.empty() && refine_set) {
+    std::fprintf(stderr, "heat: --refine needs --init-from PATH\n");
+    return 2;
+  }
+  if (!o.init_from.empty()) {
+    if (!o.resume.empty()) {
+      std::fprintf(stderr, "heat: --init-from and --resume both set the starting state: "
+                           "choose one\n");
+      return 2;
+    }
+    try {
+      const BinHeader h = bin_read_header(o.init_from);
+      o.src_rows = h.nx;
+      o.src_cols = h.ny;
+      HEAT_CHECK(h.nx >= 1 && h.ny >= 1 && h.nx <= kCoarseMaxCells && h.ny <= kCoarseMaxCells &&
+                     h.nx * h.ny <= kCoarseMaxCells,
+                 "%s holds a %lldx%lld grid: above the limit of %lld source cells (2^22)",
+                 o.init_from.c_str(), (long long)h.nx, (long long)h.ny, (long long)kCoarseMaxCells);
+      if (!refine_set) {
+        o.refine_fx = ceil_div(P.nx, h.nx);
+        o.refine_fy = ceil_div(P.ny, h.ny);
+      }
+      refine_check(P.nx, P.ny, h.nx, h.ny, o.refine_fx, o.refine_fy, o.refine_order);
+      o.src.resize(size_t(h.nx * h.ny));
+      bin_read_block(o.init_from, 0, 0, h.nx, h.ny, o.src.data(), h.ny);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "heat: --init-from: %s\n", e.what());
       return 2;
     }
   }

@@ -159,6 +159,13 @@ int heat_solver_checksum(heat_solver* s, heat_checksum* out);
    Collective; changes nothing of the run. */
 int heat_solver_coarse(heat_solver* s, int64_t fx, int64_t fy, double* sum, float* min,
                        float* max);
+/* Fill the whole plate from the cr x cc host grid S by refinement (factors fx, fy;
+   order 0 piecewise constant, 1 cell-centred bilinear; an axis wraps where the run
+   is periodic), each rank its own block where it lives, then continue at `step`
+   like heat_solver_load_owned.  Not collective; every rank passes the same S.
+   heat_solver_reset still returns to the formula initial condition. */
+int heat_solver_refine(heat_solver* s, const float* S, int64_t cr, int64_t cc, int64_t fx,
+                       int64_t fy, int order, int64_t step);
 /* rank 0: full holds nx*ny floats (row-major); other ranks: full may be NULL */
 int heat_solver_scatter(heat_solver* s, const float* full, int64_t step);
 int heat_solver_write_bin(heat_solver* s, const char* path);
@@ -268,6 +275,38 @@ int heat_op_coarse_reset(double* sum, int32_t* nmin_key, int32_t* max_key, int64
                          void* stream);
 int heat_op_checksum_raw(const float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox,
                          int64_t oy, int64_t ny, void* record, void* stream);
+/* Refinement (heat/io.hpp holds the definition).  The table of an axis of n cells
+   refined by f: n entries each of i0, i1 (int32) and w (fp32). */
+int heat_refine_axis(int64_t n, int64_t f, int order, int wrap, int32_t* i0, int32_t* i1,
+                     float* w);
+/* Fill the lx x ly block whose cell (0,0) is cell (ox, oy) of an nx x ny plate from
+   the cr x cc grid S; `wrap`: the axes that wrap (1 x, 2 y), the others clamp.
+   heat_op_refine: block and S in device memory; it builds and uploads the tables,
+   enqueues the kernel on `stream` and waits for it before it frees them.
+   heat_cpu_refine: the host twin on host memory. */
+int heat_op_refine(float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox, int64_t oy,
+                   int64_t nx, int64_t ny, const float* S, int64_t cr, int64_t cc, int64_t fx,
+                   int64_t fy, int order, int wrap, void* stream);
+int heat_cpu_refine(float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox, int64_t oy,
+                    int64_t nx, int64_t ny, const float* S, int64_t cr, int64_t cc, int64_t fx,
+                    int64_t fy, int order, int wrap);
+/* The kernel alone, for timing (tools/refine_bench.py): S and the tables of the
+   block's lx rows and ly columns already in device memory.  No allocation, copy
+   or wait. */
+int heat_op_refine_raw(float* origin, int64_t pitch, int64_t lx, int64_t ly, const float* S,
+                       int64_t cc, const int32_t* ri0, const int32_t* ri1, const float* rw,
+                       const int32_t* cj0, const int32_t* cj1, const float* cw, void* stream);
+/* The launch plan heat_op_refine takes for a block (heat::gpu::refine_plan) with the
+   planner's constants, and a cap on the waves of a launch (0 = default) for tests that
+   want every loop of the kernel to run more than once. */
+typedef struct heat_refine_plan {
+  int64_t strips, chunks, units;
+  int32_t chunk_rows, waves, align, vector_rows;
+  int32_t strip_cols, max_chunk_rows, min_chunk_rows, waves_per_cu; /* constants */
+} heat_refine_plan;
+int heat_op_refine_plan(const float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                        heat_refine_plan* out);
+int heat_op_refine_max_waves(int waves);
 /* Mirror an lx x ly field into its `depth`-deep ghost frame beyond the insulated
    sides in `sides` (1 north, 2 south, 4 west, 8 east): the device kernel, and
    its host twin on host memory. */

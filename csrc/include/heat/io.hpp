@@ -83,4 +83,46 @@ void coarse_block(const float* origin, int64_t pitch, int64_t lx, int64_t ly, in
                   int64_t oy, int64_t nx, int64_t ny, int64_t fx, int64_t fy, double* sum,
                   float* mn, float* mx);
 
+// Refinement, the inverse of the coarse view's geometry: a CR x CC source grid
+// S (CR = ceil(nx / fx), CC = ceil(ny / fy), at most kCoarseMaxCells cells)
+// fills the nx x ny plate, piecewise constant (order 0) or cell-centred
+// bilinear (order 1).  Source row I covers plate rows [lo, hi) =
+// [I*fx, min((I+1)*fx, nx)); twice its centre is the integer c2_I = lo + hi - 1.
+// Columns likewise.
+//
+// Per axis a table gives every plate index i two source indices and a weight:
+//   order 0: i0 = i1 = i / f, w = 0.
+//   order 1: t = 2i, k = the largest I with c2_I <= t (-1 if none).
+//     0 <= k < C-1:  (k, k+1, float(double(t - c2_k) / double(c2_{k+1} - c2_k)))
+//     else, no wrap or C == 1:  i0 = i1 = (k < 0 ? 0 : C-1), w = 0   (clamp)
+//     else, wrap:  (C-1, 0, float(double(t - c2_{C-1} + (k < 0 ? 2n : 0)) /
+//                                 double(c2_0 + 2n - c2_{C-1})))
+// Always 0 <= w < 1, and i0 == i1 implies w == 0.  Integers and one fp64
+// quotient rounded once to fp32: the same on every host.
+//
+// Cell (i, j), all in fp32, columns first:
+//   lerp(a, b, w) = (w == 0) ? a : fmaf(w, b - a, a)
+//   top = lerp(S[i0,j0], S[i0,j1], wy);  bot = lerp(S[i1,j0], S[i1,j1], wy)
+//   u = lerp(top, bot, wx)
+// The select makes order 0 a bit-exact copy (NaN payloads, infinities); other
+// non-finite or overflowing values follow the expression.
+struct RefineTable {
+  const int32_t* i0 = nullptr;
+  const int32_t* i1 = nullptr;
+  const float* w = nullptr;
+};
+// The table entries of plate indices [begin, begin + count) of an axis of n
+// cells refined by f.
+void refine_axis(int64_t n, int64_t f, int order, bool wrap, int64_t begin, int64_t count,
+                 int32_t* i0, int32_t* i1, float* w);
+// Throws unless fx, fy, order are valid and a CR x CC source is what
+// coarse_dims gives for the plate (the message names all four numbers).
+void refine_check(int64_t nx, int64_t ny, int64_t cr, int64_t cc, int64_t fx, int64_t fy,
+                  int order);
+// Fill the lx x ly block of host memory at `origin` from S (CC columns) and
+// the tables of the block's rows and columns (lx and ly entries): host twin of
+// gpu::refine_block.  Writes the block's cells only.
+void refine_block(float* origin, int64_t pitch, int64_t lx, int64_t ly, const float* S,
+                  int64_t cc, const RefineTable& rows, const RefineTable& cols);
+
 }  // namespace heat

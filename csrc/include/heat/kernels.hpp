@@ -15,6 +15,7 @@
 #include <cstdint>
 #include <vector>
 
+#include "heat/io.hpp"
 #include "heat/topology.hpp"
 
 namespace heat::gpu {
@@ -343,6 +344,35 @@ CoarsePlan coarse_plan(const float* origin, int64_t pitch, int64_t lx, int64_t l
                        int64_t oy, int64_t fx, int64_t fy);
 // Tests: cap the waves of a launch (0: kCoarseWavesPerCu per CU).
 void coarse_set_max_waves(int waves);
+
+// Refinement (refine.hip; definition in io.hpp): fill the lx x ly block at
+// `origin` from the source grid S (CC columns) and the tables of the block's
+// rows and columns (lx and ly entries), all device memory:
+//   u(r, c) = lerp(lerp(S[i0,j0], S[i0,j1], wy), lerp(S[i1,j0], S[i1,j1], wy), wx)
+// bit for bit what heat::refine_block gives.  Writes the block's cells only,
+// never a ghost or padding cell.  No LDS, atomics or scratch; graph-capturable,
+// no host synchronisation.
+void refine_block(float* origin, int64_t pitch, int64_t lx, int64_t ly, const float* S,
+                  int64_t cc, const RefineTable& rows, const RefineTable& cols, hipStream_t st);
+// The launch plan of refine_block.  A unit is one wave's share: a strip of
+// kRefineStripCols columns (a lane owns 4 adjacent ones; lane 0 of strip 0
+// starts on the 16-byte boundary at or below the origin, `align` columns
+// early) times a chunk of chunk_rows rows; the launch's waves grid-stride
+// over the units.
+constexpr int kRefineStripCols = 256;    // 64 lanes x float4
+constexpr int kRefineMaxChunkRows = 64;  // halved down to kRefineMinChunkRows
+constexpr int kRefineMinChunkRows = 8;   // while the units do not fill the device
+constexpr int kRefineWavesPerCu = 32;    // launch size: waves per CU
+struct RefinePlan {
+  int64_t strips = 0, chunks = 0, units = 0;
+  int chunk_rows = 0;
+  int waves = 0;             // waves launched
+  int align = 0;             // columns lane 0 of strip 0 starts before the origin
+  bool vector_rows = false;  // whole lanes store an aligned float4 (else dwords)
+};
+RefinePlan refine_plan(const float* origin, int64_t pitch, int64_t lx, int64_t ly);
+// Tests: cap the waves of a launch (0: kRefineWavesPerCu per CU).
+void refine_set_max_waves(int waves);
 
 // Device-side convergence decision (one per check, stream-ordered after the
 // residual of the check's pass and its all-reduce): the host never waits on a

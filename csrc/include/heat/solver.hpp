@@ -134,6 +134,18 @@ class Solver {
   void copy_owned(float* host, int64_t host_pitch);
   // Overwrite the owned block (and mark ghosts stale) from host memory.
   void load_owned(const float* host, int64_t host_pitch, int64_t step);
+  // Fill the whole plate from the CR x CC source grid S (host memory) by
+  // refinement with factors fx, fy (io.hpp: order 0 piecewise constant, order 1
+  // cell-centred bilinear), every rank filling its own block where it lives:
+  // no host grid, no communication.  An axis wraps where the solver's axis is
+  // periodic and clamps elsewhere (fixed and insulated edges alike); the fixed
+  // ring of a Dirichlet edge takes what the interpolation gives and is held
+  // from then on.  Makes load_owned's state transition: both fields filled,
+  // step := `step`, ghosts stale, captured graphs kept.  Not collective, but
+  // every rank must pass the same S.  reset() still returns to the formula
+  // initial condition, not to S.
+  void refine(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy, int order,
+              int64_t step);
   // Full grid on rank 0 (nx*ny row-major); empty vector on other ranks.
   std::vector<float> gather_root();
   // Inverse of gather_root: rank 0 holds the full nx*ny grid (`full`, ignored

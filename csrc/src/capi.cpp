@@ -442,6 +442,11 @@ int heat_solver_coarse(heat_solver* s, int64_t fx, int64_t fy, double* sum, floa
   });
 }
 
+int heat_solver_refine(heat_solver* s, const float* S, int64_t cr, int64_t cc, int64_t fx,
+                       int64_t fy, int order, int64_t step) {
+  return guard([&] { s->s->refine(S, cr, cc, fx, fy, order, step); });
+}
+
 int heat_solver_scatter(heat_solver* s, const float* full, int64_t step) {
   return guard([&] { s->s->scatter_root(full, step); });
 }
@@ -766,6 +771,107 @@ int heat_op_checksum_raw(const float* origin, int64_t pitch, int64_t lx, int64_t
     heat::gpu::checksum_block(origin, pitch, lx, ly, ox, oy, ny,
                               static_cast<heat::gpu::DeviceChecksum*>(record), S(stream));
   });
+}
+
+int heat_refine_axis(int64_t n, int64_t f, int order, int wrap, int32_t* i0, int32_t* i1,
+                     float* w) {
+  return guard([&] {
+    HEAT_CHECK(i0 && i1 && w, "null refine table");
+    heat::refine_axis(n, f, order, wrap != 0, 0, n, i0, i1, w);
+  });
+}
+
+namespace {
+// The tables of a block's rows then columns: i0 | i1 (each lx + ly) and w.
+struct RefineTables {
+  std::vector<int32_t> idx;
+  std::vector<float> w;
+  int64_t lx = 0, n = 0;
+  RefineTables(int64_t lx_, int64_t ly, int64_t ox, int64_t oy, int64_t nx, int64_t ny,
+               int64_t cr, int64_t cc, int64_t fx, int64_t fy, int order, int wrap)
+      : lx(lx_), n(lx_ + ly) {
+    heat::refine_check(nx, ny, cr, cc, fx, fy, order);
+    HEAT_CHECK(lx >= 0 && ly >= 0 && ox >= 0 && oy >= 0 && ox + lx <= nx && oy + ly <= ny &&
+                   (wrap & ~3) == 0,
+               "refine of a %lldx%lld block at (%lld, %lld) of a %lldx%lld plate, wrap %d",
+               (long long)lx, (long long)ly, (long long)ox, (long long)oy, (long long)nx,
+               (long long)ny, wrap);
+    idx.resize(size_t(2 * n));
+    w.resize(size_t(n));
+    heat::refine_axis(nx, fx, order, (wrap & 1) != 0, ox, lx, idx.data(), idx.data() + n, w.data());
+    heat::refine_axis(ny, fy, order, (wrap & 2) != 0, oy, ly, idx.data() + lx,
+                      idx.data() + n + lx, w.data() + lx);
+  }
+};
+}  // namespace
+
+int heat_cpu_refine(float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox, int64_t oy,
+                    int64_t nx, int64_t ny, const float* src, int64_t cr, int64_t cc, int64_t fx,
+                    int64_t fy, int order, int wrap) {
+  return guard([&] {
+    const RefineTables t(lx, ly, ox, oy, nx, ny, cr, cc, fx, fy, order, wrap);
+    const int32_t* i = t.idx.data();
+    const heat::RefineTable rows{i, i + t.n, t.w.data()};
+    const heat::RefineTable cols{i + lx, i + t.n + lx, t.w.data() + lx};
+    heat::refine_block(origin, pitch, lx, ly, src, cc, rows, cols);
+  });
+}
+
+int heat_op_refine(float* origin, int64_t pitch, int64_t lx, int64_t ly, int64_t ox, int64_t oy,
+                   int64_t nx, int64_t ny, const float* src, int64_t cr, int64_t cc, int64_t fx,
+                   int64_t fy, int order, int wrap, void* stream) {
+  return guard([&] {
+    const RefineTables t(lx, ly, ox, oy, nx, ny, cr, cc, fx, fy, order, wrap);
+    if (lx == 0 || ly == 0) return;
+    float* dw = nullptr;
+    HIP_CHECK(hipMalloc(&dw, size_t(3 * t.n) * 4));
+    int32_t* di = reinterpret_cast<int32_t*>(dw + t.n);
+    try {
+      HIP_CHECK(hipMemcpyAsync(dw, t.w.data(), size_t(t.n) * 4, hipMemcpyHostToDevice, S(stream)));
+      HIP_CHECK(
+          hipMemcpyAsync(di, t.idx.data(), size_t(2 * t.n) * 4, hipMemcpyHostToDevice, S(stream)));
+      const heat::RefineTable rows{di, di + t.n, dw};
+      const heat::RefineTable cols{di + lx, di + t.n + lx, dw + lx};
+      heat::gpu::refine_block(origin, pitch, lx, ly, src, cc, rows, cols, S(stream));
+      HIP_CHECK(hipStreamSynchronize(S(stream)));
+    } catch (...) {
+      (void)hipFree(dw);
+      throw;
+    }
+    HIP_CHECK(hipFree(dw));
+  });
+}
+
+int heat_op_refine_raw(float* origin, int64_t pitch, int64_t lx, int64_t ly, const float* src,
+                       int64_t cc, const int32_t* ri0, const int32_t* ri1, const float* rw,
+                       const int32_t* cj0, const int32_t* cj1, const float* cw, void* stream) {
+  return guard([&] {
+    heat::gpu::refine_block(origin, pitch, lx, ly, src, cc, heat::RefineTable{ri0, ri1, rw},
+                            heat::RefineTable{cj0, cj1, cw}, S(stream));
+  });
+}
+
+int heat_op_refine_plan(const float* origin, int64_t pitch, int64_t lx, int64_t ly,
+                        heat_refine_plan* out) {
+  return guard([&] {
+    const heat::gpu::RefinePlan p = heat::gpu::refine_plan(origin, pitch, lx, ly);
+    std::memset(out, 0, sizeof *out);
+    out->strips = p.strips;
+    out->chunks = p.chunks;
+    out->units = p.units;
+    out->chunk_rows = p.chunk_rows;
+    out->waves = p.waves;
+    out->align = p.align;
+    out->vector_rows = p.vector_rows;
+    out->strip_cols = heat::gpu::kRefineStripCols;
+    out->max_chunk_rows = heat::gpu::kRefineMaxChunkRows;
+    out->min_chunk_rows = heat::gpu::kRefineMinChunkRows;
+    out->waves_per_cu = heat::gpu::kRefineWavesPerCu;
+  });
+}
+
+int heat_op_refine_max_waves(int waves) {
+  return guard([&] { heat::gpu::refine_set_max_waves(waves); });
 }
 
 int heat_op_fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,

@@ -257,4 +257,87 @@ void coarse_block(const float* origin, int64_t pitch, int64_t lx, int64_t ly, in
   }
 }
 
+void refine_axis(int64_t n, int64_t f, int order, bool wrap, int64_t begin, int64_t count,
+                 int32_t* i0, int32_t* i1, float* w) {
+  HEAT_CHECK(n >= 1 && f >= 1 && (order == 0 || order == 1),
+             "refine axis: n %lld, factor %lld, order %d", (long long)n, (long long)f, order);
+  HEAT_CHECK(begin >= 0 && count >= 0 && begin + count <= n, "refine axis: [%lld, %lld) of %lld",
+             (long long)begin, (long long)(begin + count), (long long)n);
+  const int64_t C = ceil_div(n, f);
+  HEAT_CHECK(C <= kCoarseMaxCells, "refine axis: %lld source cells", (long long)C);
+  auto c2 = [&](int64_t I) { return I * f + std::min((I + 1) * f, n) - 1; };
+  for (int64_t q = 0; q < count; ++q) {
+    const int64_t i = begin + q;
+    int64_t a, b;
+    float wt = 0.f;
+    if (order == 0) {
+      a = b = i / f;
+    } else {
+      // The cell of i is I = i / f; c2 of the next cell is above 2i, c2 of the
+      // one before is not: k is I or I - 1.
+      const int64_t t = 2 * i, I = i / f, k = c2(I) <= t ? I : I - 1;
+      if (k >= 0 && k < C - 1) {
+        a = k;
+        b = k + 1;
+        wt = float(double(t - c2(k)) / double(c2(k + 1) - c2(k)));
+      } else if (!wrap || C == 1) {
+        a = b = k < 0 ? 0 : C - 1;
+      } else {
+        a = C - 1;
+        b = 0;
+        wt = float(double(t - c2(C - 1) + (k < 0 ? 2 * n : 0)) / double(c2(0) + 2 * n - c2(C - 1)));
+      }
+    }
+    i0[q] = int32_t(a);
+    i1[q] = int32_t(b);
+    w[q] = wt;
+  }
+}
+
+void refine_check(int64_t nx, int64_t ny, int64_t cr, int64_t cc, int64_t fx, int64_t fy,
+                  int order) {
+  HEAT_CHECK(order == 0 || order == 1, "refine order %d: expected 0 or 1", order);
+  int64_t r = 0, c = 0;
+  coarse_dims(nx, ny, fx, fy, &r, &c);
+  HEAT_CHECK(r == cr && c == cc,
+             "refine: a %lldx%lld source grid does not fit factors %lldx%lld on a %lldx%lld plate, "
+             "which need a %lldx%lld grid",
+             (long long)cr, (long long)cc, (long long)fx, (long long)fy, (long long)nx,
+             (long long)ny, (long long)r, (long long)c);
+}
+
+namespace {
+inline float refine_lerp(float a, float b, float w) {
+  return w == 0.f ? a : std::fmaf(w, b - a, a);
+}
+}  // namespace
+
+void refine_block(float* origin, int64_t pitch, int64_t lx, int64_t ly, const float* S,
+                  int64_t cc, const RefineTable& rows, const RefineTable& cols) {
+  if (lx <= 0 || ly <= 0) return;
+  HEAT_CHECK(origin && S && pitch >= ly && cc >= 1 && rows.i0 && rows.i1 && rows.w && cols.i0 &&
+                 cols.i1 && cols.w,
+             "refine of a %lldx%lld block", (long long)lx, (long long)ly);
+  // The column pass of a source row pair is reused while the pair stays.
+  std::vector<float> top(static_cast<size_t>(ly)), bot(static_cast<size_t>(ly));
+  int32_t pa = -1, pb = -1;
+  for (int64_t r = 0; r < lx; ++r) {
+    const int32_t a = rows.i0[r], b = rows.i1[r];
+    if (a != pa || b != pb) {
+      const float* sa = S + int64_t(a) * cc;
+      const float* sb = S + int64_t(b) * cc;
+      for (int64_t c = 0; c < ly; ++c) {
+        const int32_t j0 = cols.i0[c], j1 = cols.i1[c];
+        top[size_t(c)] = refine_lerp(sa[j0], sa[j1], cols.w[c]);
+        bot[size_t(c)] = refine_lerp(sb[j0], sb[j1], cols.w[c]);
+      }
+      pa = a;
+      pb = b;
+    }
+    float* dst = origin + r * pitch;
+    const float wx = rows.w[r];
+    for (int64_t c = 0; c < ly; ++c) dst[c] = refine_lerp(top[size_t(c)], bot[size_t(c)], wx);
+  }
+}
+
 }  // namespace heat

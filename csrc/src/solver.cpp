@@ -1806,6 +1806,56 @@ void Solver::load_owned(const float* host, int64_t host_pitch, int64_t step) {
   gr_ = gc_ = 0;
 }
 
+void Solver::refine(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy, int order,
+                    int64_t step) {
+  complete_pending();
+  TraceRange tr("heat.refine");
+  HEAT_CHECK(S != nullptr, "refine: null source grid");
+  refine_check(P_.nx, P_.ny, CR, CC, fx, fy, order);
+  // This rank's rows [ox, ox + lx) and columns [oy, oy + ly) of the tables.
+  const int64_t lx = blk_.lx, ly = blk_.ly, n = lx + ly;
+  std::vector<int32_t> idx(static_cast<size_t>(2 * n));
+  std::vector<float> wt(static_cast<size_t>(n));
+  int32_t* i0 = idx.data();
+  int32_t* i1 = idx.data() + n;
+  refine_axis(P_.nx, fx, order, (P_.periodic & kPeriodicX) != 0, blk_.ox, lx, i0, i1, wt.data());
+  refine_axis(P_.ny, fy, order, (P_.periodic & kPeriodicY) != 0, blk_.oy, ly, i0 + lx, i1 + lx,
+              wt.data() + lx);
+  synchronize();
+  if (on_gpu()) {
+    // One allocation: S, the weights, the indices (all 4-byte words).
+    const size_t cells = size_t(CR * CC);
+    float* d = nullptr;
+    HIP_CHECK(hipMalloc(&d, (cells + size_t(3 * n)) * 4));
+    float* dw = d + cells;
+    int32_t* di = reinterpret_cast<int32_t*>(dw + n);
+    hipError_t e = hipMemcpyAsync(d, S, cells * 4, hipMemcpyHostToDevice, s_comp_);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(dw, wt.data(), size_t(n) * 4, hipMemcpyHostToDevice, s_comp_);
+    if (e == hipSuccess)
+      e = hipMemcpyAsync(di, idx.data(), size_t(2 * n) * 4, hipMemcpyHostToDevice, s_comp_);
+    if (e != hipSuccess) {
+      (void)hipFree(d);
+      HIP_CHECK(e);
+    }
+    const RefineTable rows{di, di + n, dw}, cols{di + lx, di + n + lx, dw + lx};
+    try {
+      for (int b = 0; b < 2; ++b)
+        gpu::refine_block(field_[b], L_.pitch, lx, ly, d, CC, rows, cols, s_comp_);
+      synchronize();
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    HIP_CHECK(hipFree(d));
+  } else {
+    const RefineTable rows{i0, i1, wt.data()}, cols{i0 + lx, i1 + lx, wt.data() + lx};
+    for (int b = 0; b < 2; ++b) refine_block(field_[b], L_.pitch, lx, ly, S, CC, rows, cols);
+  }
+  step_ = step;
+  gr_ = gc_ = 0;
+}
+
 void Solver::scatter_root(const float* full, int64_t step) {
   complete_pending();
   TraceRange tr("heat.scatter");

@@ -122,6 +122,13 @@ class HeatCoarsePlan(Structure):
                 ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32), ("pad_", c_int32)]
 
 
+class HeatRefinePlan(Structure):
+    _fields_ = [("strips", c_int64), ("chunks", c_int64), ("units", c_int64),
+                ("chunk_rows", c_int32), ("waves", c_int32), ("align", c_int32),
+                ("vector_rows", c_int32), ("strip_cols", c_int32), ("max_chunk_rows", c_int32),
+                ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32)]
+
+
 class HeatChecksum(Structure):
     _fields_ = [("hash", c_uint64), ("sum", c_double), ("min", c_double), ("max", c_double),
                 ("count", c_int64)]
@@ -208,6 +215,16 @@ _SIGS = {
     "heat_op_coarse_raw": (c_int, [c_void_p] + [c_int64] * 9 + [c_void_p] * 4),
     "heat_op_coarse_reset": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),
     "heat_op_checksum_raw": (c_int, [c_void_p] + [c_int64] * 6 + [c_void_p, c_void_p]),
+    "heat_solver_refine": (c_int, [c_void_p, c_void_p] + [c_int64] * 4 + [c_int, c_int64]),
+    "heat_refine_axis": (c_int, [c_int64, c_int64, c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "heat_op_refine": (c_int, [c_void_p] + [c_int64] * 7 + [c_void_p] + [c_int64] * 4
+                       + [c_int, c_int, c_void_p]),
+    "heat_cpu_refine": (c_int, [c_void_p] + [c_int64] * 7 + [c_void_p] + [c_int64] * 4
+                        + [c_int, c_int]),
+    "heat_op_refine_raw": (c_int, [c_void_p] + [c_int64] * 3 + [c_void_p, c_int64]
+                           + [c_void_p] * 7),
+    "heat_op_refine_plan": (c_int, [c_void_p] + [c_int64] * 3 + [POINTER(HeatRefinePlan)]),
+    "heat_op_refine_max_waves": (c_int, [c_int]),
     "heat_op_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int, c_int,
                                               c_void_p]),
     "heat_cpu_fill_insulated_ghosts": (c_int, [c_void_p, c_int64, c_int64, c_int64, c_int,
@@ -321,7 +338,11 @@ def check(rc: int) -> None:
 
 
 def call(name: str, *args):
-    check(getattr(lib(), name)(*args))
+    fn = getattr(lib(), name, None)
+    if fn is None:
+        raise NativeError(f"{LIB_PATH} has no entry point {name}: it is older than this package; "
+                          "rebuild it with `make`")
+    check(fn(*args))
 
 
 def loaded_path() -> str:
@@ -349,7 +370,7 @@ def rccl_unique_id() -> bytes:
 
 __all__ = [
     "HeatParams", "HeatComm", "HeatMsg", "HeatTransportInfo", "HeatTbTuning", "HeatRunStats", "HeatBlockInfo", "HeatChecksum",
-    "HeatCoarsePlan",
+    "HeatCoarsePlan", "HeatRefinePlan",
     "SENDRECV_CB", "ALLREDUCE_CB", "BARRIER_CB", "NativeError", "lib", "call", "check",
     "available", "build_native", "loaded_path", "device_count", "rccl_unique_id",
     "require_gpu_native", "LIB_PATH", "CLI_PATH", "c_uint", "EXP_PATH", "load_exp", "unload_exp",

@@ -14,6 +14,7 @@ from __future__ import annotations
 
 import argparse
 import json
+import struct
 import subprocess
 import sys
 
@@ -59,6 +60,15 @@ def build_parser() -> argparse.ArgumentParser:
            "else binary")
     a("--coarse-stat", choices=["mean", "min", "max"], default="mean",
       help="the value written per coarse cell")
+    a("--init-from", default=None, metavar="PATH",
+      help="start from a coarse grid: a binary grid file (what --coarse-out writes) refined "
+           "onto the plate on the device; overrides --init, the run starts at step 0; not with "
+           "--resume")
+    a("--refine", default=None, metavar="FX[xFY]",
+      help="its integer factors (FY = FX if omitted); the file must hold ceil(nx/FX) x "
+           "ceil(ny/FY) values (default: ceil(nx/rows) x ceil(ny/cols))")
+    a("--refine-order", type=int, choices=[0, 1], default=1,
+      help="0 piecewise constant, 1 cell-centred bilinear")
     a("--naming", choices=["plain", "mpi", "cuda"], default="plain")
     a("--dump-initial", action="store_true")
     a("--compat", choices=["none", "mpi", "cuda"], default=None)
@@ -93,7 +103,7 @@ def build_parser() -> argparse.ArgumentParser:
     return p
 
 
-def parse_coarse(text: str):
+def parse_coarse(text: str, flag: str = "--coarse"):
     """"FX" or "FXxFY" -> (fx, fy); ValueError if malformed or a factor < 1."""
     parts = text.lower().split("x")
     try:
@@ -101,11 +111,33 @@ def parse_coarse(text: str):
     except ValueError:
         f = []
     if len(f) not in (1, 2):
-        raise ValueError(f"--coarse {text}: expected FX or FXxFY (integer factors)")
+        raise ValueError(f"{flag} {text}: expected FX or FXxFY (integer factors)")
     fx, fy = f[0], f[-1]
     if fx < 1 or fy < 1:
-        raise ValueError(f"--coarse {text}: a factor must be >= 1")
+        raise ValueError(f"{flag} {text}: a factor must be >= 1")
     return fx, fy
+
+
+def load_init_from(path: str, refine, order: int, nx: int, ny: int):
+    """The source grid of --init-from and its factors: (S, fx, fy).  ValueError
+    if the file's dimensions are not what the factors give for the plate."""
+    from .ops import coarse_dims
+    try:
+        h = hio.read_bin_header(path)
+    except (OSError, struct.error) as e:
+        raise ValueError(f"cannot read {path}: {e}")
+    cr, cc = int(h["nx"]), int(h["ny"])
+    limit = 1 << 22
+    if cr < 1 or cc < 1 or cr * cc > limit:
+        raise ValueError(f"{path} holds a {cr}x{cc} grid: above the limit of {limit} source "
+                         "cells (2^22)")
+    fx, fy = refine if refine is not None else (-(-nx // cr), -(-ny // cc))
+    r, c = coarse_dims(nx, ny, fx, fy)
+    if (r, c) != (cr, cc):
+        raise ValueError(f"refine: a {cr}x{cc} source grid does not fit factors {fx}x{fy} on a "
+                         f"{nx}x{ny} plate, which need a {r}x{c} grid")
+    S, _ = hio.read_bin(path, mmap=False)
+    return S, fx, fy
 
 
 def main(argv=None) -> int:
@@ -128,6 +160,18 @@ def main(argv=None) -> int:
             coarse_dims(args.nx, args.ny, *coarse)
         except (ValueError, _native.NativeError) as e:
             parser.error(f"--coarse: {e}" if not str(e).startswith("--coarse") else str(e))
+    init_from = None
+    if args.refine is not None and args.init_from is None:
+        parser.error("--refine needs --init-from PATH")
+    if args.init_from is not None:
+        if args.resume:
+            parser.error("--init-from and --resume both set the starting state: choose one")
+        try:
+            refine = None if args.refine is None else parse_coarse(args.refine, "--refine")
+            init_from = load_init_from(args.init_from, refine, args.refine_order, args.nx,
+                                       args.ny)
+        except (ValueError, _native.NativeError) as e:
+            parser.error(f"--init-from: {e}" if not str(e).startswith("--refine") else str(e))
     if args.gpus > 0 or args.plan:
         # Single-process native modes: the `heat` binary owns the threads
         # and the planner; same flags, same output.
@@ -161,6 +205,12 @@ def main(argv=None) -> int:
     if args.resume:
         solver.load(args.resume)
 
+    def start():
+        if init_from is not None:
+            solver.refine(init_from[0], init_from[1], init_from[2], order=args.refine_order)
+
+    start()
+
     small = cfg.nx * cfg.ny <= (1 << 24)
     if args.naming == "mpi":
         init_path, final_path = "initial_im.dat", "final_im.dat"
@@ -193,6 +243,7 @@ def main(argv=None) -> int:
             raise SystemExit("--warmup with --resume")
         solver.run(args.warmup)
         solver.reset()
+        start()
     if args.dump_initial or args.naming == "mpi":
         emit(init_path)
     total = cfg.total_steps()
@@ -248,7 +299,11 @@ def main(argv=None) -> int:
                 t_compute=acc["t_compute"], t_reduce=acc["t_reduce"],
                 insulated=solver.info.insulated, periodic=solver.info.periodic,
                 native=_native.loaded_path(),
-                **({"coarse": coarse_info} if coarse_info else {})) + "\n")
+                **({"coarse": coarse_info} if coarse_info else {}),
+                **({"init_from": {"path": args.init_from, "rows": int(init_from[0].shape[0]),
+                                  "cols": int(init_from[0].shape[1]), "fx": init_from[1],
+                                  "fy": init_from[2], "order": args.refine_order}}
+                   if init_from is not None else {})) + "\n")
         out.flush()
     solver.barrier()
     solver.close()

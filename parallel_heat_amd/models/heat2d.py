@@ -291,6 +291,28 @@ class HeatSolver:
             mean = s / count
         return {"mean": mean, "sum": s, "min": mn, "max": mx, "count": count}
 
+    def refine(self, S: np.ndarray, fx: Optional[int] = None, fy: Optional[int] = None,
+               order: int = 1, step: int = 0) -> None:
+        """Start from a coarse grid: fill the whole plate from the (CR, CC)
+        source grid S by refinement with integer factors fx, fy, each rank its
+        own block where the field lives (no host grid, no communication):
+        piecewise constant (order 0) or cell-centred bilinear (order 1), the
+        inverse of coarse()'s geometry (reference.refine_np is the definition).
+        S must be (ceil(nx/fx), ceil(ny/fy)); a factor left out is inferred as
+        ceil(n / S.shape).  An axis wraps where the run is periodic and clamps
+        elsewhere; the fixed ring of a Dirichlet edge takes what the
+        interpolation gives.  The run continues at `step` like after scatter().
+        Not collective, but every rank must pass the same S.  reset() still
+        returns to the configured initial condition, not to S."""
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        if S.ndim != 2 or S.size == 0:
+            raise ValueError(f"source grid shape {S.shape}: expected (rows, cols)")
+        cr, cc = S.shape
+        fx = -(-self.config.nx // cr) if fx is None else int(fx)
+        fy = -(-self.config.ny // cc) if fy is None else int(fy)
+        _native.call("heat_solver_refine", self._h, S.ctypes.data, cr, cc, fx, fy, int(order),
+                     int(step))
+
     def save(self, path: str) -> None:
         """Binary grid / checkpoint (header + nx*ny fp32); collective."""
         _native.call("heat_solver_write_bin", self._h, str(path).encode())

@@ -227,6 +227,75 @@ def fma32(a, b, c) -> np.ndarray:
         return s.astype(np.float32)
 
 
+def refine_axis_np(n: int, f: int, order: int = 1, wrap: bool = False):
+    """The refinement table of an axis of n cells refined by the factor f,
+    NumPy only: (i0, i1) int32 source indices and w float32 for every index.
+    Source cell I covers [I*f, min((I+1)*f, n)); twice its centre is
+    c2_I = lo + hi - 1.  Order 0: i0 = i1 = i // f, w = 0.  Order 1: with
+    t = 2i and k the largest I with c2_I <= t (-1 if none), an index between
+    two centres gets (k, k+1, (t - c2_k) / (c2_{k+1} - c2_k)); one outside them
+    clamps to the nearest cell with w = 0, or with `wrap` (and more than one
+    cell) gets (C-1, 0, (t - c2_{C-1} [+ 2n if k < 0]) / (c2_0 + 2n - c2_{C-1})).
+    The quotient is taken in float64 and rounded once to float32."""
+    n, f, order = int(n), int(f), int(order)
+    if n < 1 or f < 1 or order not in (0, 1):
+        raise ValueError(f"refine axis: n {n}, factor {f}, order {order}")
+    i = np.arange(n, dtype=np.int64)
+    if order == 0:
+        k = (i // f).astype(np.int32)
+        return k, k.copy(), np.zeros(n, np.float32)
+    C = -(-n // f)
+    I = np.arange(C, dtype=np.int64)
+    c2 = I * f + np.minimum((I + 1) * f, n) - 1
+    t = 2 * i
+    k = np.searchsorted(c2, t, side="right") - 1
+    i0 = np.clip(k, 0, C - 1)
+    i1 = i0.copy()
+    w = np.zeros(n, np.float64)
+    inner = (k >= 0) & (k < C - 1)
+    ki = k[inner]
+    i1[inner] = ki + 1
+    w[inner] = (t[inner] - c2[ki]).astype(np.float64) / (c2[ki + 1] - c2[ki]).astype(np.float64)
+    if wrap and C > 1:
+        outer = ~inner
+        i0[outer] = C - 1
+        i1[outer] = 0
+        num = t[outer] - c2[C - 1] + np.where(k[outer] < 0, 2 * n, 0)
+        w[outer] = num.astype(np.float64) / np.float64(c2[0] + 2 * n - c2[C - 1])
+    return i0.astype(np.int32), i1.astype(np.int32), w.astype(np.float32)
+
+
+def _lerp32(a, b, w) -> np.ndarray:
+    """(w == 0) ? a : fmaf(w, b - a, a) in float32; the select keeps a's bits."""
+    a, b, w = np.broadcast_arrays(np.asarray(a, np.float32), np.asarray(b, np.float32),
+                                  np.asarray(w, np.float32))
+    with np.errstate(invalid="ignore", over="ignore"):
+        d = b - a
+        return np.where(w == 0, a, fma32(w, d, a))
+
+
+def refine_np(S: np.ndarray, nx: int, ny: int, fx: int, fy: int, order: int = 1,
+              periodic: str = "") -> np.ndarray:
+    """The nx x ny plate refined from the (ceil(nx/fx), ceil(ny/fy)) source grid
+    S, NumPy only, bit for bit what the engine's refine gives: piecewise
+    constant (order 0) or cell-centred bilinear (order 1), an axis in
+    `periodic` wrapping, the others clamping.  With the tables of
+    refine_axis_np, in float32, columns first:
+        top = lerp(S[i0, j0], S[i0, j1], wy);  bot = lerp(S[i1, j0], S[i1, j1], wy)
+        u = lerp(top, bot, wx),   lerp(a, b, w) = a if w == 0 else fma(w, b - a, a)"""
+    S = np.ascontiguousarray(S, np.float32)
+    nx, ny, fx, fy = int(nx), int(ny), int(fx), int(fy)
+    per = periodic_axes(periodic)
+    if fx < 1 or fy < 1 or S.ndim != 2 or S.shape != (-(-nx // fx), -(-ny // fy)):
+        raise ValueError(f"refine: a {S.shape} source grid does not fit factors {fx}x{fy} on a "
+                         f"{nx}x{ny} plate")
+    i0, i1, wx = refine_axis_np(nx, fx, order, "x" in per)
+    j0, j1, wy = refine_axis_np(ny, fy, order, "y" in per)
+    top = _lerp32(S[i0][:, j0], S[i0][:, j1], wy[None, :])
+    bot = _lerp32(S[i1][:, j0], S[i1][:, j1], wy[None, :])
+    return np.ascontiguousarray(_lerp32(top, bot, wx[:, None]))
+
+
 def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
                 insulated: str = "", periodic: str = "") -> np.ndarray:
     """One step with the engine's default numerics, bit for bit: the

@@ -16,6 +16,7 @@ import enum
 from dataclasses import dataclass, field
 from typing import List, Optional, Sequence, Tuple
 
+import numpy as np
 import torch
 
 from .. import _native
@@ -423,6 +424,66 @@ def set_coarse_max_waves(waves: int) -> None:
     """Cap the waves of a `coarse` launch (0: the default, from the CU count):
     tests make the kernel's grid-stride loop run more than once with it."""
     _native.call("heat_op_coarse_max_waves", int(waves))
+
+
+def _wrap_mask(wrap: str) -> int:
+    if any(c not in "xy" for c in wrap):
+        raise ValueError(f"wrap={wrap!r}; expected any of the letters 'xy'")
+    return (1 if "x" in wrap else 0) | (2 if "y" in wrap else 0)
+
+
+def refine_axis(n: int, f: int, order: int = 1, wrap: bool = False):
+    """The engine's refinement table of an axis of n cells refined by f
+    (heat::refine_axis): NumPy arrays i0, i1 (int32) and w (float32)."""
+    n = int(n)
+    i0 = np.empty(max(n, 0), np.int32)
+    i1 = np.empty(max(n, 0), np.int32)
+    w = np.empty(max(n, 0), np.float32)
+    _native.call("heat_refine_axis", n, int(f), int(order), int(bool(wrap)),
+                 ctypes.c_void_p(i0.ctypes.data), ctypes.c_void_p(i1.ctypes.data),
+                 ctypes.c_void_p(w.ctypes.data))
+    return i0, i1, w
+
+
+def refine(f: Field, S, fx: int, fy: int, order: int = 1, wrap: str = "", ox: int = 0,
+           oy: int = 0, nx: Optional[int] = None, ny: Optional[int] = None) -> None:
+    """Fill the field's owned block, placed at (ox, oy) of an nx x ny plate
+    (default: the block is the plate), from the (ceil(nx/fx), ceil(ny/fy))
+    source grid S by refinement: piecewise constant (order 0) or cell-centred
+    bilinear (order 1), the axes in `wrap` (letters of "xy") wrapping, the
+    others clamping (reference.refine_np is the definition).  Writes owned
+    cells only.  The device kernel on a GPU field (enqueued on the current
+    stream and waited for), the host heat::refine_block on a CPU field."""
+    nx = f.lx if nx is None else int(nx)
+    ny = f.ly if ny is None else int(ny)
+    if not isinstance(S, torch.Tensor):
+        S = torch.from_numpy(np.array(S, dtype=np.float32))  # a copy: S may be read-only
+    S = S.to(device=f.device, dtype=torch.float32).contiguous()
+    if S.dim() != 2:
+        raise ValueError(f"source grid shape {tuple(S.shape)}: expected (rows, cols)")
+    args = (ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly, int(ox), int(oy), nx, ny,
+            ctypes.c_void_p(S.data_ptr()), int(S.shape[0]), int(S.shape[1]), int(fx), int(fy),
+            int(order), _wrap_mask(wrap))
+    if f.device.type == "cpu":
+        _native.call("heat_cpu_refine", *args)
+    else:
+        _native.call("heat_op_refine", *args, ctypes.c_void_p(_stream()))
+
+
+def refine_plan(f: Field) -> dict:
+    """The launch plan `refine` takes for this GPU field (strips, chunks, units,
+    chunk_rows, waves, align, vector_rows) together with the planner's constants
+    strip_cols, max_chunk_rows, min_chunk_rows and waves_per_cu."""
+    p = _native.HeatRefinePlan()
+    _native.call("heat_op_refine_plan", ctypes.c_void_p(f.ptr()), f.pitch, f.lx, f.ly,
+                 ctypes.byref(p))
+    return {k: int(getattr(p, k)) for k, _ in p._fields_}
+
+
+def set_refine_max_waves(waves: int) -> None:
+    """Cap the waves of a `refine` launch (0: the default, from the CU count):
+    tests make the kernel's grid-stride loop run more than once with it."""
+    _native.call("heat_op_refine_max_waves", int(waves))
 
 
 def fill_insulated_ghosts(f: Field, sides: str, depth: int) -> None:
