@@ -134,6 +134,24 @@ refine-selftest-asan: $(BUILD)/refine-selftest-asan
 	ASAN_OPTIONS=detect_leaks=1 $(BUILD)/refine-selftest-asan
 .PHONY: refine-selftest refine-selftest-asan
 
+# The same for the heat source (the host twin of the source step and the
+# extended-table builder of its ghost cells).
+SOURCE_SELFTEST_SRCS := csrc/tests/source_selftest.cpp csrc/src/common.cpp csrc/src/topology.cpp \
+                        csrc/src/io.cpp csrc/src/cpu_backend.cpp
+$(BUILD)/source-selftest: $(SOURCE_SELFTEST_SRCS) $(HDRS)
+	@mkdir -p $(BUILD)
+	g++ -std=c++17 -O2 -g -Wall -Icsrc/include -mfma -mavx2 -fopenmp $(SOURCE_SELFTEST_SRCS) -o $@
+$(BUILD)/source-selftest-asan: $(SOURCE_SELFTEST_SRCS) $(HDRS)
+	@mkdir -p $(BUILD)
+	g++ -std=c++17 -O1 -g -Wall -Icsrc/include -mfma -mavx2 -fopenmp \
+	  -fsanitize=address,undefined -fno-omit-frame-pointer -fno-sanitize-recover=all \
+	  $(SOURCE_SELFTEST_SRCS) -o $@
+source-selftest: $(BUILD)/source-selftest
+	$(BUILD)/source-selftest
+source-selftest-asan: $(BUILD)/source-selftest-asan
+	ASAN_OPTIONS=detect_leaks=1 $(BUILD)/source-selftest-asan
+.PHONY: source-selftest source-selftest-asan
+
 # Reference-compatible program names (mpi/Makefile:12-22, cuda/Makefile:13):
 #   make ref-variants SIZE=900 STEPS=10000 STEP=20 THREADS=4
 # writes build/ref/{heat_N,heat_omp_N,heat_con_N,heat_con_omp_N,cuda_heat}; run

@@ -40,7 +40,8 @@ void usage() {
       "  --eps F                 convergence threshold on max|delta|    [1e-3]\n"
       "  --backend cpu|hip       compute backend                        [hip if a GPU exists]\n"
       "  --threads N             CPU OpenMP threads                     [runtime default]\n"
-      "  --kernel auto|tb|lds|mfma|naive  GPU kernel family (auto = tb)  [auto]\n"
+      "  --kernel auto|tb|lds|mfma|naive|src  GPU kernel family (auto = tb; src with\n"
+      "                          --source-from)                          [auto]\n"
       "  --tb-depth K            fused steps per pass (= halo depth)    [8 hip, 1 cpu]\n"
       "  --decomp auto|rows|2d   process grid (auto = MPI_Dims_create)  [auto]\n"
       "  --px P --py Q           explicit process grid\n"
@@ -60,6 +61,12 @@ void usage() {
       "  --refine FX[xFY]        its integer factors (FY = FX if omitted); the file must hold\n"
       "                          ceil(nx/FX) x ceil(ny/FY) values  [ceil(nx/rows) x ceil(ny/cols)]\n"
       "  --refine-order 0|1      piecewise constant, or cell-centred bilinear            [1]\n"
+      "  --source-from PATH      a static heat source: a binary grid file refined onto the plate\n"
+      "                          like --init-from's; every step then adds it, u' = A u + q, with\n"
+      "                          the one-step src kernel (--kernel auto becomes src); not with\n"
+      "                          --numerics mpi; checkpoints do not store it\n"
+      "  --source-refine FX[xFY] its integer factors           [ceil(nx/rows) x ceil(ny/cols)]\n"
+      "  --source-order 0|1      piecewise constant, or cell-centred bilinear            [1]\n"
       "  --naming plain|mpi|cuda reference-style file names and messages [plain]\n"
       "  --dump-initial          also write the initial grid\n"
       "  --compat none|mpi|cuda  reference step-count/check semantics   [none]\n"
@@ -108,6 +115,11 @@ struct Options {
   int64_t refine_fx = 0, refine_fy = 0, src_rows = 0, src_cols = 0;
   int refine_order = 1;
   std::vector<float> src;  // the file's grid, read once in main
+  // Heat source (--source-from PATH --source-refine FX[xFY] --source-order K).
+  std::string source_from;
+  int64_t source_fx = 0, source_fy = 0, q_rows = 0, q_cols = 0;
+  int source_order = 1;
+  std::vector<float> q_map;  // the file's grid, read once in main
 };
 
 // "FX" or "FXxFY" -> the factors; false if malformed (a factor < 1 parses).
@@ -175,6 +187,8 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
     }
   } registered{reg, rank};
   if (reg) reg->set(rank, &S);
+  if (!o.source_from.empty())
+    S.set_source(o.q_map.data(), o.q_rows, o.q_cols, o.source_fx, o.source_fy, o.source_order);
   if (!o.resume.empty()) S.read_bin(o.resume);
   auto start = [&] {
     if (!o.init_from.empty())
@@ -355,6 +369,17 @@ void run_rank(const Options& o, const Params& P, std::unique_ptr<Transport> tr,
                     path.c_str(), (long long)o.src_rows, (long long)o.src_cols,
                     (long long)o.refine_fx, (long long)o.refine_fy, o.refine_order);
       }
+      if (!o.source_from.empty()) {
+        std::string path;  // JSON string escapes
+        for (char ch : o.source_from) {
+          if (ch == '"' || ch == '\\') path += '\\';
+          path += ch;
+        }
+        std::printf(", \"source\": {\"path\": \"%s\", \"rows\": %lld, \"cols\": %lld, "
+                    "\"fx\": %lld, \"fy\": %lld, \"order\": %d}",
+                    path.c_str(), (long long)o.q_rows, (long long)o.q_cols,
+                    (long long)o.source_fx, (long long)o.source_fy, o.source_order);
+      }
       std::printf("}\n");
     }
     std::fflush(stdout);
@@ -373,6 +398,7 @@ int main(int argc, char** argv) {
   bool plan = false;
   bool coarse_set = false;
   bool refine_set = false;
+  bool source_refine_set = false;
   int port = 0;
   for (int i = 1; i < argc; ++i) {
     std::string a = argv[i];
@@ -411,6 +437,7 @@ int main(int argc, char** argv) {
                  : k == "tb"  ? KernelKind::TB
                  : k == "lds" ? KernelKind::Lds
                  : k == "mfma" ? KernelKind::Mfma
+                 : k == "src" ? KernelKind::Source
                               : KernelKind::Auto;
     } else if (a == "--tb-depth") P.tb_depth = std::atoi(need().c_str());
     else if (a == "--decomp") {
@@ -513,6 +540,28 @@ int main(int argc, char** argv) {
       }
       o.refine_order = s == "1";
     }
+    else if (a == "--source-from") o.source_from = need();
+    else if (a == "--source-refine") {
+      const std::string s = need();
+      if (!parse_coarse(s, &o.source_fx, &o.source_fy)) {
+        std::fprintf(stderr, "heat: --source-refine %s: expected FX or FXxFY (integer factors)\n",
+                     s.c_str());
+        return 2;
+      }
+      if (o.source_fx < 1 || o.source_fy < 1) {
+        std::fprintf(stderr, "heat: --source-refine %s: a factor must be >= 1\n", s.c_str());
+        return 2;
+      }
+      source_refine_set = true;
+    }
+    else if (a == "--source-order") {
+      const std::string s = need();
+      if (s != "0" && s != "1") {
+        std::fprintf(stderr, "heat: --source-order %s: expected 0 or 1\n", s.c_str());
+        return 2;
+      }
+      o.source_order = s == "1";
+    }
     else if (a == "--plan") plan = true;
     else { std::fprintf(stderr, "unknown option %s\n", a.c_str()); usage(); return 2; }
   }
@@ -564,6 +613,48 @@ int main(int argc, char** argv) {
       return 2;
     }
   }
+  if (o.source_from.empty() && source_refine_set) {
+    std::fprintf(stderr, "heat: --source-refine needs --source-from PATH\n");
+    return 2;
+  }
+  if (!o.source_from.empty()) {
+    if (P.numerics != Numerics::Fp32) {
+      std::fprintf(stderr, "heat: --source-from needs --numerics fp32: the source step evaluates "
+                           "the canonical fp32 expression only\n");
+      return 2;
+    }
+    if (P.kernel != KernelKind::Auto && P.kernel != KernelKind::Source) {
+      std::fprintf(stderr, "heat: --source-from runs the src kernel: --kernel %s has no source "
+                           "term\n", kernel_name(P.kernel));
+      return 2;
+    }
+    P.source = true;
+    P.kernel = KernelKind::Source;
+    try {
+      const BinHeader h = bin_read_header(o.source_from);
+      o.q_rows = h.nx;
+      o.q_cols = h.ny;
+      HEAT_CHECK(h.nx >= 1 && h.ny >= 1 && h.nx <= kCoarseMaxCells && h.ny <= kCoarseMaxCells &&
+                     h.nx * h.ny <= kCoarseMaxCells,
+                 "%s holds a %lldx%lld grid: above the limit of %lld source cells (2^22)",
+                 o.source_from.c_str(), (long long)h.nx, (long long)h.ny,
+                 (long long)kCoarseMaxCells);
+      if (!source_refine_set) {
+        o.source_fx = ceil_div(P.nx, h.nx);
+        o.source_fy = ceil_div(P.ny, h.ny);
+      }
+      refine_check(P.nx, P.ny, h.nx, h.ny, o.source_fx, o.source_fy, o.source_order);
+      o.q_map.resize(size_t(h.nx * h.ny));
+      bin_read_block(o.source_from, 0, 0, h.nx, h.ny, o.q_map.data(), h.ny);
+    } catch (const std::exception& e) {
+      std::fprintf(stderr, "heat: --source-from: %s\n", e.what());
+      return 2;
+    }
+  } else if (P.kernel == KernelKind::Source) {
+    std::fprintf(stderr, "heat: --kernel src is the kernel of a run with a heat source: it needs "
+                         "--source-from PATH\n");
+    return 2;
+  }
   if (o.naming == "mpi" && P.compat == Compat::None) P.compat = Compat::Mpi;
   if (o.naming == "cuda" && P.compat == Compat::None) P.compat = Compat::Cuda;
 
@@ -575,7 +666,9 @@ int main(int argc, char** argv) {
     // exchange fields on small blocks; the worst rank decides.
     const int ranks = std::max(gpus, env_i("WORLD_SIZE", 1));
     const Cart cart(ranks, P.decomp, P.px, P.py, P.nx, P.ny);
-    const int depth = P.tb_depth > 0 ? P.tb_depth : 12;
+    // A run with a heat source (--source-from): one-step passes (depth 1 unless
+    // --tb-depth), a third field, never resident tiles.
+    const int depth = P.tb_depth > 0 ? P.tb_depth : P.source ? 1 : 12;
     // Passes per exchange as the solver picks them (resident-aware unless
     // --halo-passes is given; resident_halo_passes), with the host-side
     // gfx950 resident fit: whether every rank's span box runs as one-round
@@ -600,7 +693,7 @@ int main(int argc, char** argv) {
       const Block b = make_block(cart, r, P.nx, P.ny, P.periodic);
       const int sh = shape(ghosts ? span_box(cart, b, depth, m, P.insulated, P.periodic)
                                   : Box{0, b.lx, 0, b.ly});
-      resident = resident && sh != 0;
+      resident = resident && sh != 0 && !P.source;
       if (r == 0) res_rows = sh >> 8, res_waves = sh & 255;
     }
     int64_t worst = 0, worst_rank = 0;
@@ -611,11 +704,11 @@ int main(int argc, char** argv) {
       if (cart.py > 1) h = std::min<int64_t>(h, b.ly);
       if (edge) h = std::min<int64_t>(h, ext);
       const Layout L = Layout::make(b.lx, b.ly, int(std::max<int64_t>(1, h)));
-      int64_t bytes = 2 * L.bytes();
+      int64_t bytes = (P.source ? 3 : 2) * L.bytes();
       // Resident workgroup tiles (blocks under 64 strip-rows per SIMD on the
       // 1024 SIMDs of an MI355X) add two exchange fields of the same layout.
       const int64_t strip = 256 - 2 * ((depth + 3) / 4 * 4);
-      if ((b.ly + strip - 1) / strip * b.lx < 64 * 1024) bytes += 2 * L.bytes();
+      if (!P.source && (b.ly + strip - 1) / strip * b.lx < 64 * 1024) bytes += 2 * L.bytes();
       if (cart.py > 1) bytes += 4 * b.lx * h * 4;
       if (cart.px > 1 && cart.py > 1) bytes += 8 * h * h * 4;
       if (bytes > worst) worst = bytes, worst_rank = r;

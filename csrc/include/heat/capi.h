@@ -43,6 +43,15 @@ typedef struct heat_params {
   int32_t periodic;    /* periodic (wrap-around) axes: 1 x (north-south joined), 2 y (west-east) */
 } heat_params;
 
+/* Options added after heat_params was frozen (heat_solver_create_ex).  `size` is
+ * sizeof(heat_params_ext) as the caller knows it: fields beyond it take their
+ * defaults, so later options need no new entry point. */
+typedef struct heat_params_ext {
+  int32_t size;
+  int32_t source;  /* 1: the run has a per-cell heat source (heat_solver_set_source):
+                      u' = stencil(u) + q, the src kernel, a third field */
+} heat_params_ext;
+
 /* Transport selection for heat_solver_create. */
 typedef struct heat_comm {
   int32_t kind;          /* 0 local, 1 rccl, 2 tcp, 3 callback, 4 loopback (ctx = hub) */
@@ -115,6 +124,11 @@ int heat_transport_create(const heat_comm* c, heat_transport** out);
 int heat_transport_destroy(heat_transport* t);
 int heat_transport_info_get(heat_transport* t, heat_transport_info* out);
 int heat_solver_create_shared(const heat_params* p, heat_transport* t, heat_solver** out);
+/* The same with the extended options (ext may be NULL: the defaults). */
+int heat_solver_create_ex(const heat_params* p, const heat_params_ext* ext, const heat_comm* c,
+                          heat_solver** out);
+int heat_solver_create_shared_ex(const heat_params* p, const heat_params_ext* ext,
+                                 heat_transport* t, heat_solver** out);
 int heat_solver_destroy(heat_solver* s);
 int heat_solver_run(heat_solver* s, int64_t steps, heat_run_stats* out);
 /* Asynchronous run (plain GPU runs): enqueue the steps and return; the next
@@ -166,6 +180,16 @@ int heat_solver_coarse(heat_solver* s, int64_t fx, int64_t fy, double* sum, floa
    heat_solver_reset still returns to the formula initial condition. */
 int heat_solver_refine(heat_solver* s, const float* S, int64_t cr, int64_t cc, int64_t fx,
                        int64_t fy, int order, int64_t step);
+/* Heat source of a solver created with heat_params_ext.source: q = the refinement
+   of the cr x cc host grid S (factors, order, limits and wrapping of
+   heat_solver_refine), filled into the rank's block and its ghost ring without
+   communication; S == NULL clears it (all +0).  Not part of the state: reset,
+   refine, load, scatter and read_bin keep it, checkpoints do not store it.  Not
+   collective; every rank passes the same S.  Fails on a solver without the option. */
+int heat_solver_set_source(heat_solver* s, const float* S, int64_t cr, int64_t cc, int64_t fx,
+                           int64_t fy, int order);
+/* Tests: the source field's rows and columns [-halo, l + halo) of this rank. */
+int heat_solver_copy_source(heat_solver* s, float* host, int64_t host_pitch, int halo);
 /* rank 0: full holds nx*ny floats (row-major); other ranks: full may be NULL */
 int heat_solver_scatter(heat_solver* s, const float* full, int64_t step);
 int heat_solver_write_bin(heat_solver* s, const char* path);
@@ -194,6 +218,31 @@ int heat_op_lds_step(const float* src, float* dst, int64_t pitch, int64_t gx0, i
 int heat_op_mfma_step(const float* src, float* dst, int64_t pitch, int64_t gx0, int64_t gy0,
                       int64_t nx, int64_t ny, float cx, float cy, int64_t r0, int64_t r1,
                       int64_t c0, int64_t c1, unsigned* resid, void* stream);
+/* One step with a per-cell source q (the layout of src and dst):
+   u' = stencil(u) + q over the box, fp32 numerics; `gate` (may be NULL): a device
+   word, non-zero = the launch writes nothing.  Device kernel and host twin. */
+int heat_op_source_step(const float* src, float* dst, const float* q, int64_t pitch, int64_t gx0,
+                        int64_t gy0, int64_t nx, int64_t ny, float cx, float cy, int64_t r0,
+                        int64_t r1, int64_t c0, int64_t c1, unsigned* resid, void* stream,
+                        const unsigned* gate);
+int heat_cpu_source_step(const float* src, float* dst, const float* q, int64_t pitch, int64_t gx0,
+                         int64_t gy0, int64_t nx, int64_t ny, float cx, float cy, int64_t r0,
+                         int64_t r1, int64_t c0, int64_t c1, float* resid /* may be NULL */);
+/* The launch plan heat_op_source_step takes (heat::gpu::source_plan) with the
+   planner's constants, a cap on the waves of a launch (0 = default) for tests, and
+   the switch of non-temporal q loads and dst stores (1 on, 0 off, -1 = the default:
+   on when a step sweeps more than 256 MiB).  Both knobs are for tests and
+   tools/source_bench.py only: they are process-global and change every launch
+   of every solver in the process. */
+typedef struct heat_source_plan {
+  int64_t strips, chunks, units;
+  int32_t chunk_rows, waves, align, vector_rows;
+  int32_t strip_cols, max_chunk_rows, min_chunk_rows, waves_per_cu; /* constants */
+} heat_source_plan;
+int heat_op_source_plan(const float* src, const float* dst, const float* q, int64_t pitch,
+                        int64_t r0, int64_t r1, int64_t c0, int64_t c1, heat_source_plan* out);
+int heat_op_source_max_waves(int waves);
+int heat_op_source_nontemporal(int mode);
 // Diagnostics: per-wave start/end clock stamps of subsequent TB launches
 // (4 u64 per wave: start, end at 100 MHz, block, strip<<32|chunk); null = off.
 int heat_op_tb_stamps(void* buf, int64_t waves);

@@ -30,6 +30,14 @@ void init_field(float* origin, const Layout& L, int64_t gx0, int64_t gy0, int64_
 // NaN if any cell became NaN) when want_resid, else 0.
 float step(const float* src, float* dst, const Geom& g, const Box& box, bool want_resid);
 
+// Host twin of gpu::source_step (kernels.hpp): the same step with a static
+// per-cell source q in the layout of src and dst,
+//   u' = heat::stencil(c, n, s, w, e, cx, cy) + q
+// one rounded fp32 add after the unchanged FMA expression; a cell the step
+// does not update ignores q.  fp32 numerics only.
+float step_source(const float* src, float* dst, const float* q, const Geom& g, const Box& box,
+                  bool want_resid);
+
 // Host twin of gpu::fill_insulated_ghosts (kernels.hpp): mirror the field
 // into the `depth`-deep ghost frame beyond the insulated sides in `sides`.
 void fill_insulated_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int sides,

@@ -115,6 +115,18 @@ struct RefineTable {
 // cells refined by f.
 void refine_axis(int64_t n, int64_t f, int order, bool wrap, int64_t begin, int64_t count,
                  int32_t* i0, int32_t* i1, float* w);
+// The plate index whose value a cell at index i of an axis of n cells holds,
+// i possibly beyond the plate (a ghost cell): i itself inside the plate,
+// i mod n on a wrapped (periodic) axis, the mirror image -i or 2(n-1) - i
+// beyond a mirrored (insulated) end, else the nearest plate index (beyond a
+// fixed end, which no update reaches).
+int64_t ghost_axis_index(int64_t i, int64_t n, bool wrap, bool mirror_lo, bool mirror_hi);
+// refine_axis for indices [begin, begin + count) that may lie beyond the plate:
+// entry q is the plate's table entry at ghost_axis_index(begin + q).  A field
+// that is a function of the plate index alone (the heat source) gets its ghost
+// cells this way, without communication.
+void refine_axis_ext(int64_t n, int64_t f, int order, bool wrap, bool mirror_lo, bool mirror_hi,
+                     int64_t begin, int64_t count, int32_t* i0, int32_t* i1, float* w);
 // Throws unless fx, fy, order are valid and a CR x CC source is what
 // coarse_dims gives for the plate (the message names all four numbers).
 void refine_check(int64_t nx, int64_t ny, int64_t cr, int64_t cc, int64_t fx, int64_t fy,

@@ -374,6 +374,49 @@ RefinePlan refine_plan(const float* origin, int64_t pitch, int64_t lx, int64_t l
 // Tests: cap the waves of a launch (0: kRefineWavesPerCu per CU).
 void refine_set_max_waves(int waves);
 
+// One Jacobi step with a static per-cell heat source over `box` (source.hip):
+//   u' = heat::stencil(c, n, s, w, e, cx, cy) + q
+// one rounded fp32 add after the unchanged FMA expression; q has the layout of
+// src and dst (the same pitch, cell (0, 0) at the pointer).  lds_step's
+// contract: only cells with 1 <= gx <= nx-2 and 1 <= gy <= ny-2 are updated
+// (a fixed cell keeps its value and ignores q), the box alone is written, a
+// closed g.gate writes nothing, and with resid the max |new - old| over the
+// box's updated cells is max-reduced as float bits (a NaN on top) with one
+// atomic per workgroup.  Reads u in rows [r0-1, r1] x columns [c0-1, c1] and q
+// in the box, nothing else.  fp32 numerics only.  Two LDS words (the
+// residual), no scratch; graph-capturable, no host synchronisation.
+void source_step(const float* src, float* dst, const float* q, const StencilGeom& g,
+                 const Box& box, unsigned* resid, hipStream_t st);
+// The launch plan of source_step.  A unit is one wave's share: a strip of
+// kSourceStripCols columns (a lane owns 4 adjacent ones; lane 0 of strip 0
+// starts on the 16-byte boundary at or below the box's first column, `align`
+// columns early) times a chunk of chunk_rows rows, streamed with a 3-row
+// window in registers; the launch's waves grid-stride over the units.
+constexpr int kSourceStripCols = 256;    // 64 lanes x float4
+constexpr int kSourceMaxChunkRows = 64;  // shortened, down to kSourceMinChunkRows,
+constexpr int kSourceMinChunkRows = 8;   // while the units do not fill one round of the launch
+constexpr int kSourceWavesPerCu = 16;    // launch size: waves per CU (half the occupancy: at
+                                         // 8192^2 4096 waves ran 1.2x faster than 7104,
+                                         // profiles/source.md)
+struct SourcePlan {
+  int64_t strips = 0, chunks = 0, units = 0;
+  int chunk_rows = 0;
+  int waves = 0;             // waves launched
+  int align = 0;             // columns lane 0 of strip 0 starts before the box
+  bool vector_rows = false;  // whole lanes move aligned float4s (else dwords): the pitch is
+                             // a multiple of 4 and the three arrays share their 16-byte phase
+};
+SourcePlan source_plan(const float* src, const float* dst, const float* q, int64_t pitch,
+                       const Box& box);
+// Tests: cap the waves of a launch (0: kSourceWavesPerCu per CU, at most the
+// kernel's resident waves).
+void source_set_max_waves(int waves);
+// Tests and tools/source_bench.py only (process-global: it changes every
+// launch of every solver in the process): q loads and dst stores non-temporal
+// (1) or plain (0); -1, the default: by the bytes a step sweeps, non-temporal
+// above the Infinity Cache's 256 MiB (profiles/source.md).
+void source_set_nontemporal(int mode);
+
 // Device-side convergence decision (one per check, stream-ordered after the
 // residual of the check's pass and its all-reduce): the host never waits on a
 // check.  Unless the gate is already closed, judge_check compares the

@@ -32,6 +32,8 @@ enum class KernelKind : int {
   Lds = 3,    // LDS-staged halo tile, one step per launch (also --numerics mpi)
   Mfma = 4,   // the stencil as banded matmuls on fp32 MFMA, one step per launch
               // (an experiment: not bitwise equal to the others; see mfma.hip)
+  Source = 5, // "src": one step per launch with a per-cell heat source,
+              // u' = stencil(u) + q (source.hip); the kernel of Params::source runs
 };
 
 // Reference-compatibility switches.
@@ -104,6 +106,11 @@ struct Params {
   // are joined), bit 1 = y (columns: west and east joined).  An axis cannot
   // be periodic and have an insulated side.  See kPeriodicAll.
   uint8_t periodic = 0;
+  // The run has a static per-cell heat source q (Solver::set_source), all
+  // +0 until one is set: u' = stencil(u) + q.  Declared at construction, where
+  // the kernel family (KernelKind::Source), T and H are fixed; it costs a
+  // third field and runs one step per pass over memory.
+  bool source = false;
 };
 
 constexpr uint8_t kInsulatedAll = 15;

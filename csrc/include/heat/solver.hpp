@@ -146,6 +146,21 @@ class Solver {
   // initial condition, not to S.
   void refine(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy, int order,
               int64_t step);
+  // Heat source (Params::source): q = refine(S, fx, fy, order) with refine()'s
+  // geometry and limits, every rank filling its own block AND its ghost ring
+  // where they live.  q is a function of the plate index alone, so a ghost
+  // cell takes the value of the plate cell it stands for (io.hpp:
+  // ghost_axis_index: the neighbour's cell, the wrapped or the mirrored one),
+  // per axis, hence right in every corner: deep-halo passes, which update
+  // part of the ghost ring redundantly, need no exchange for it.  S == nullptr
+  // clears the source (every cell +0).  The source is not part of the state:
+  // reset, refine, load_owned, scatter_root and read_bin keep it, checkpoints
+  // do not store it, and captured graphs are kept (they hold the pointer).
+  // Not collective, but every rank must pass the same S.
+  void set_source(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy, int order);
+  // Copy the source field's rows and columns [-halo, l + halo) to host memory
+  // (tests: the ghost rule); halo <= halo().
+  void copy_source(float* host, int64_t host_pitch, int halo);
   // Full grid on rank 0 (nx*ny row-major); empty vector on other ranks.
   std::vector<float> gather_root();
   // Inverse of gather_root: rank 0 holds the full nx*ny grid (`full`, ignored
@@ -327,6 +342,9 @@ class Solver {
 
   float* base_[2] = {nullptr, nullptr};
   float* field_[2] = {nullptr, nullptr};
+  // The heat source (Params::source): a third field of the same layout.
+  float* qbase_ = nullptr;
+  float* q_ = nullptr;
   // Contiguous E/W halo buffers (send W, send E, recv W, recv E).
   float* ew_[4] = {nullptr, nullptr, nullptr, nullptr};
   // Ghost-corner buffers of 2-D grids (send NW NE SW SE, recv NW NE SW SE).

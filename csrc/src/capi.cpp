@@ -35,6 +35,7 @@ const char* kernel_name(KernelKind k) {
     case KernelKind::TB: return "tb";
     case KernelKind::Lds: return "lds";
     case KernelKind::Mfma: return "mfma";
+    case KernelKind::Source: return "src";
   }
   return "?";
 }
@@ -211,6 +212,18 @@ heat::gpu::StencilGeom geom(int64_t pitch, int64_t gx0, int64_t gy0, int64_t nx,
   g.cy = cy;
   return g;
 }
+
+// heat_params plus the size-prefixed extension: a field the caller's struct
+// is too short for keeps its default.
+heat::Params params_from_c_ext(const heat_params* p, const heat_params_ext* ext) {
+  heat::Params P = heat::params_from_c(p);
+  if (ext) {
+    HEAT_CHECK(ext->size >= int32_t(sizeof(int32_t)), "heat_params_ext.size %d", ext->size);
+    if (size_t(ext->size) >= offsetof(heat_params_ext, source) + sizeof ext->source)
+      P.source = ext->source != 0;
+  }
+  return P;
+}
 }  // namespace
 
 namespace heat::gpu {
@@ -258,8 +271,17 @@ int heat_loopback_hub_fail(void* hub) {
 }
 
 int heat_solver_create(const heat_params* p, const heat_comm* c, heat_solver** out) {
+  return heat_solver_create_ex(p, nullptr, c, out);
+}
+
+int heat_solver_create_shared(const heat_params* p, heat_transport* t, heat_solver** out) {
+  return heat_solver_create_shared_ex(p, nullptr, t, out);
+}
+
+int heat_solver_create_ex(const heat_params* p, const heat_params_ext* ext, const heat_comm* c,
+                          heat_solver** out) {
   return guard([&] {
-    heat::Params P = heat::params_from_c(p);
+    heat::Params P = params_from_c_ext(p, ext);
     std::shared_ptr<heat::Transport> tr = make_transport(c);
     if (P.device < 0 && c && (c->kind == 1 || c->kind == 4)) P.device = c->device;
     auto* h = new heat_solver;
@@ -303,10 +325,11 @@ int heat_transport_info_get(heat_transport* t, heat_transport_info* out) {
   });
 }
 
-int heat_solver_create_shared(const heat_params* p, heat_transport* t, heat_solver** out) {
+int heat_solver_create_shared_ex(const heat_params* p, const heat_params_ext* ext,
+                                 heat_transport* t, heat_solver** out) {
   return guard([&] {
     HEAT_CHECK(t != nullptr && t->t != nullptr, "null transport");
-    heat::Params P = heat::params_from_c(p);
+    heat::Params P = params_from_c_ext(p, ext);
     if (P.device < 0) P.device = t->device;
     auto* h = new heat_solver;
     try {
@@ -447,6 +470,15 @@ int heat_solver_refine(heat_solver* s, const float* S, int64_t cr, int64_t cc, i
   return guard([&] { s->s->refine(S, cr, cc, fx, fy, order, step); });
 }
 
+int heat_solver_set_source(heat_solver* s, const float* S, int64_t cr, int64_t cc, int64_t fx,
+                           int64_t fy, int order) {
+  return guard([&] { s->s->set_source(S, cr, cc, fx, fy, order); });
+}
+
+int heat_solver_copy_source(heat_solver* s, float* host, int64_t host_pitch, int halo) {
+  return guard([&] { s->s->copy_source(host, host_pitch, halo); });
+}
+
 int heat_solver_scatter(heat_solver* s, const float* full, int64_t step) {
   return guard([&] { s->s->scatter_root(full, step); });
 }
@@ -531,6 +563,63 @@ int heat_op_lds_step(const float* src, float* dst, int64_t pitch, int64_t gx0, i
     g.numerics = numerics;
     heat::gpu::lds_step(src, dst, g, heat::Box{r0, r1, c0, c1}, resid, S(stream));
   });
+}
+
+int heat_op_source_step(const float* src, float* dst, const float* q, int64_t pitch, int64_t gx0,
+                        int64_t gy0, int64_t nx, int64_t ny, float cx, float cy, int64_t r0,
+                        int64_t r1, int64_t c0, int64_t c1, unsigned* resid, void* stream,
+                        const unsigned* gate) {
+  return guard([&] {
+    auto g = geom(pitch, gx0, gy0, nx, ny, cx, cy);
+    g.gate = gate;
+    heat::gpu::source_step(src, dst, q, g, heat::Box{r0, r1, c0, c1}, resid, S(stream));
+  });
+}
+
+int heat_cpu_source_step(const float* src, float* dst, const float* q, int64_t pitch, int64_t gx0,
+                         int64_t gy0, int64_t nx, int64_t ny, float cx, float cy, int64_t r0,
+                         int64_t r1, int64_t c0, int64_t c1, float* resid) {
+  return guard([&] {
+    heat::cpu::Geom g;
+    g.pitch = pitch;
+    g.gx0 = gx0;
+    g.gy0 = gy0;
+    g.nx = nx;
+    g.ny = ny;
+    g.cx = cx;
+    g.cy = cy;
+    const float r =
+        heat::cpu::step_source(src, dst, q, g, heat::Box{r0, r1, c0, c1}, resid != nullptr);
+    if (resid) *resid = r;
+  });
+}
+
+int heat_op_source_plan(const float* src, const float* dst, const float* q, int64_t pitch,
+                        int64_t r0, int64_t r1, int64_t c0, int64_t c1, heat_source_plan* out) {
+  return guard([&] {
+    const heat::gpu::SourcePlan p =
+        heat::gpu::source_plan(src, dst, q, pitch, heat::Box{r0, r1, c0, c1});
+    std::memset(out, 0, sizeof *out);
+    out->strips = p.strips;
+    out->chunks = p.chunks;
+    out->units = p.units;
+    out->chunk_rows = p.chunk_rows;
+    out->waves = p.waves;
+    out->align = p.align;
+    out->vector_rows = p.vector_rows;
+    out->strip_cols = heat::gpu::kSourceStripCols;
+    out->max_chunk_rows = heat::gpu::kSourceMaxChunkRows;
+    out->min_chunk_rows = heat::gpu::kSourceMinChunkRows;
+    out->waves_per_cu = heat::gpu::kSourceWavesPerCu;
+  });
+}
+
+int heat_op_source_max_waves(int waves) {
+  return guard([&] { heat::gpu::source_set_max_waves(waves); });
+}
+
+int heat_op_source_nontemporal(int mode) {
+  return guard([&] { heat::gpu::source_set_nontemporal(mode); });
 }
 
 int heat_op_mfma_step(const float* src, float* dst, int64_t pitch, int64_t gx0, int64_t gy0,

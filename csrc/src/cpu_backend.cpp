@@ -27,7 +27,11 @@ void init_field(float* origin, const Layout& L, int64_t gx0, int64_t gy0, int64_
 
 static inline bool interior(int64_t g, int64_t n) { return g >= 1 && g <= n - 2; }
 
-float step(const float* src, float* dst, const Geom& g, const Box& box, bool want_resid) {
+namespace {
+// Q: the step adds the source q (same layout) to every cell it updates.
+template <bool Q>
+float step_impl(const float* src, float* dst, const float* q, const Geom& g, const Box& box,
+                bool want_resid) {
   if (box.empty()) return 0.0f;
   uint32_t mbits = 0;
   // Only the global-interior part of each row is updated; boundary cells are
@@ -47,7 +51,8 @@ float step(const float* src, float* dst, const Geom& g, const Box& box, bool wan
     uint32_t rm = 0;
     auto row = [&](auto update) {
       for (int64_t c = cl; c < ch; ++c) {
-        const float v = update(s[c], n[c], so[c], s[c - 1], s[c + 1], g.cx, g.cy);
+        float v = update(s[c], n[c], so[c], s[c - 1], s[c + 1], g.cx, g.cy);
+        if constexpr (Q) v = v + q[r * g.pitch + c];  // one rounded add, nothing fused into it
         d[c] = v;
         if (want_resid) {
           float diff = std::fabs(v - s[c]);
@@ -71,6 +76,18 @@ float step(const float* src, float* dst, const Geom& g, const Box& box, bool wan
   float m;
   std::memcpy(&m, &mbits, 4);
   return want_resid ? m : 0.0f;
+}
+}  // namespace
+
+float step(const float* src, float* dst, const Geom& g, const Box& box, bool want_resid) {
+  return step_impl<false>(src, dst, nullptr, g, box, want_resid);
+}
+
+float step_source(const float* src, float* dst, const float* q, const Geom& g, const Box& box,
+                  bool want_resid) {
+  HEAT_CHECK(q != nullptr, "source step without a source field");
+  HEAT_CHECK(g.numerics == 0, "the source step evaluates the canonical fp32 expression only");
+  return step_impl<true>(src, dst, q, g, box, want_resid);
 }
 
 void fill_edge_ghosts(float* origin, int64_t pitch, int64_t lx, int64_t ly, int insulated_sides,

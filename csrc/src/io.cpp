@@ -294,6 +294,22 @@ void refine_axis(int64_t n, int64_t f, int order, bool wrap, int64_t begin, int6
   }
 }
 
+int64_t ghost_axis_index(int64_t i, int64_t n, bool wrap, bool mirror_lo, bool mirror_hi) {
+  if (i >= 0 && i < n) return i;
+  if (wrap) return ((i % n) + n) % n;
+  const int64_t m = i < 0 ? (mirror_lo ? -i : 0) : (mirror_hi ? 2 * (n - 1) - i : n - 1);
+  return std::min(std::max<int64_t>(m, 0), n - 1);  // a mirror deeper than the plate: clamped
+}
+
+void refine_axis_ext(int64_t n, int64_t f, int order, bool wrap, bool mirror_lo, bool mirror_hi,
+                     int64_t begin, int64_t count, int32_t* i0, int32_t* i1, float* w) {
+  HEAT_CHECK(n >= 1 && count >= 0, "refine axis: %lld entries of %lld cells", (long long)count,
+             (long long)n);
+  for (int64_t q = 0; q < count; ++q)
+    refine_axis(n, f, order, wrap, ghost_axis_index(begin + q, n, wrap, mirror_lo, mirror_hi), 1,
+                i0 + q, i1 + q, w + q);
+}
+
 void refine_check(int64_t nx, int64_t ny, int64_t cr, int64_t cc, int64_t fx, int64_t fy,
                   int order) {
   HEAT_CHECK(order == 0 || order == 1, "refine order %d: expected 0 or 1", order);

@@ -69,6 +69,19 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   HEAT_CHECK((P_.periodic & ~kPeriodicAll) == 0, "periodic axes %d", int(P_.periodic));
   if (const char* axis = periodic_clash(P_.insulated, P_.periodic))
     HEAT_CHECK(false, "axis %s is periodic and has an insulated side: choose one", axis);
+  // A heat source has an update of its own, u' = stencil(u) + q, which only
+  // the one-step src kernel (and the CPU backend's twin) evaluates.
+  if (P_.source) {
+    HEAT_CHECK(P_.numerics == Numerics::Fp32,
+               "a heat source (source) needs --numerics fp32, not %s", numerics_name(P_.numerics));
+    HEAT_CHECK(P_.kernel == KernelKind::Auto || P_.kernel == KernelKind::Source,
+               "a heat source (source) runs the src kernel: --kernel %s has no source term",
+               kernel_name(P_.kernel));
+    P_.kernel = KernelKind::Source;
+  } else {
+    HEAT_CHECK(P_.kernel != KernelKind::Source,
+               "--kernel src is the kernel of a run with a heat source: set the source option");
+  }
   cart_ = Cart(tr_->world(), P_.decomp, P_.px, P_.py, P_.nx, P_.ny);
   blk_ = make_block(cart_, tr_->rank(), P_.nx, P_.ny, P_.periodic);
   if (on_gpu()) {
@@ -258,6 +271,11 @@ void Solver::alloc() {
       HIP_CHECK(hipMalloc(&base_[i], size_t(L_.bytes())));
       field_[i] = base_[i] + L_.origin();
     }
+    if (P_.source) {  // the source field: every cell +0 until set_source
+      HIP_CHECK(hipMalloc(&qbase_, size_t(L_.bytes())));
+      HIP_CHECK(hipMemset(qbase_, 0, size_t(L_.bytes())));
+      q_ = qbase_ + L_.origin();
+    }
     if (cart_.py > 1)
       for (auto& b : ew_) HIP_CHECK(hipMalloc(&b, ew_elems * 4));
     if (cart_.px > 1 && cart_.py > 1)
@@ -309,6 +327,12 @@ void Solver::alloc() {
                  (long long)L_.bytes());
       field_[i] = base_[i] + L_.origin();
     }
+    if (P_.source) {
+      qbase_ = static_cast<float*>(std::aligned_alloc(256, size_t(round_up(L_.bytes(), 256))));
+      HEAT_CHECK(qbase_ != nullptr, "host allocation of %lld bytes failed", (long long)L_.bytes());
+      std::memset(qbase_, 0, size_t(L_.bytes()));
+      q_ = qbase_ + L_.origin();
+    }
     if (cart_.py > 1)
       for (auto& b : ew_) {
         b = static_cast<float*>(std::malloc(ew_elems * 4));
@@ -337,6 +361,7 @@ void Solver::free_all() {
     staged_calls_.clear();
     for (auto& b : base_)
       if (b) (void)hipFree(b);
+    if (qbase_) (void)hipFree(qbase_);
     for (auto& b : ew_)
       if (b) (void)hipFree(b);
     for (auto& b : cn_)
@@ -364,10 +389,12 @@ void Solver::free_all() {
     if (s_comm_) (void)hipStreamDestroy(s_comm_);
   } else {
     for (auto& b : base_) std::free(b);
+    std::free(qbase_);
     for (auto& b : ew_) std::free(b);
     for (auto& b : cn_) std::free(b);
   }
   for (auto& b : base_) b = nullptr;
+  qbase_ = q_ = nullptr;
   for (auto& b : ew_) b = nullptr;
   for (auto& b : cn_) b = nullptr;
   for (int i = 0; i < kMaxMsgs; ++i) stage_send_[i] = stage_recv_[i] = nullptr;
@@ -744,7 +771,9 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
       const float* a = field_[cur_];
       float* d = field_[cur_ ^ 1];
       unsigned* rj = j == rl - 1 ? r : nullptr;
-      if (P_.kernel == KernelKind::Lds)
+      if (P_.kernel == KernelKind::Source)
+        gpu::source_step(a, d, q_, g, b, rj, st);
+      else if (P_.kernel == KernelKind::Lds)
         gpu::lds_step(a, d, g, b, rj, st);
       else if (P_.kernel == KernelKind::Mfma)
         gpu::mfma_step(a, d, g, b, rj, st);
@@ -941,7 +970,8 @@ void Solver::compute_cpu(int k, int rl, int64_t er, int64_t ec) {
     Box b{open_side(North) ? -(er + e) : 0, blk_.lx + (open_side(South) ? er + e : 0),
           open_side(West) ? -(ec + e) : 0, blk_.ly + (open_side(East) ? ec + e : 0)};
     const bool at = j == rl - 1;
-    float r = cpu::step(field_[cur_], field_[cur_ ^ 1], g, b, at);
+    const float r = P_.source ? cpu::step_source(field_[cur_], field_[cur_ ^ 1], q_, g, b, at)
+                              : cpu::step(field_[cur_], field_[cur_ ^ 1], g, b, at);
     if (at) cpu_resid_ = r;
     cur_ ^= 1;
   }
@@ -1854,6 +1884,77 @@ void Solver::refine(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t 
   }
   step_ = step;
   gr_ = gc_ = 0;
+}
+
+void Solver::set_source(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy,
+                        int order) {
+  complete_pending();
+  TraceRange tr("heat.set_source");
+  HEAT_CHECK(P_.source,
+             "set_source: this solver was built without a heat source; set the source option "
+             "(Params::source, HeatConfig.source, --source-from) when it is created");
+  synchronize();
+  if (S == nullptr) {  // every allocated cell +0
+    if (on_gpu()) {
+      HIP_CHECK(hipMemsetAsync(qbase_, 0, size_t(L_.bytes()), s_comp_));
+      synchronize();
+    } else {
+      std::memset(qbase_, 0, size_t(L_.bytes()));
+    }
+    return;
+  }
+  refine_check(P_.nx, P_.ny, CR, CC, fx, fy, order);
+  // The block extended by the ghost depth: rows [-H, lx + H), columns
+  // [-H, ly + H), each index mapped to the plate cell it stands for.
+  const int64_t H = H_, ex = blk_.lx + 2 * H, ey = blk_.ly + 2 * H, n = ex + ey;
+  std::vector<int32_t> idx(static_cast<size_t>(2 * n));
+  std::vector<float> wt(static_cast<size_t>(n));
+  int32_t* i0 = idx.data();
+  int32_t* i1 = idx.data() + n;
+  refine_axis_ext(P_.nx, fx, order, (P_.periodic & kPeriodicX) != 0, insulated(North),
+                  insulated(South), blk_.ox - H, ex, i0, i1, wt.data());
+  refine_axis_ext(P_.ny, fy, order, (P_.periodic & kPeriodicY) != 0, insulated(West),
+                  insulated(East), blk_.oy - H, ey, i0 + ex, i1 + ex, wt.data() + ex);
+  float* origin = q_ - H * L_.pitch - H;
+  if (on_gpu()) {
+    // One allocation: S, the weights, the indices (all 4-byte words).
+    const size_t cells = size_t(CR * CC);
+    float* d = nullptr;
+    HIP_CHECK(hipMalloc(&d, (cells + size_t(3 * n)) * 4));
+    float* dw = d + cells;
+    int32_t* di = reinterpret_cast<int32_t*>(dw + n);
+    try {
+      HIP_CHECK(hipMemcpyAsync(d, S, cells * 4, hipMemcpyHostToDevice, s_comp_));
+      HIP_CHECK(hipMemcpyAsync(dw, wt.data(), size_t(n) * 4, hipMemcpyHostToDevice, s_comp_));
+      HIP_CHECK(hipMemcpyAsync(di, idx.data(), size_t(2 * n) * 4, hipMemcpyHostToDevice, s_comp_));
+      const RefineTable rows{di, di + n, dw}, cols{di + ex, di + n + ex, dw + ex};
+      gpu::refine_block(origin, L_.pitch, ex, ey, d, CC, rows, cols, s_comp_);
+      synchronize();
+    } catch (...) {
+      (void)hipFree(d);
+      throw;
+    }
+    HIP_CHECK(hipFree(d));
+  } else {
+    const RefineTable rows{i0, i1, wt.data()}, cols{i0 + ex, i1 + ex, wt.data() + ex};
+    refine_block(origin, L_.pitch, ex, ey, S, CC, rows, cols);
+  }
+}
+
+void Solver::copy_source(float* host, int64_t host_pitch, int halo) {
+  complete_pending();
+  HEAT_CHECK(P_.source, "copy_source: this solver was built without a heat source");
+  HEAT_CHECK(halo >= 0 && halo <= H_, "copy_source: halo %d beyond the ghost depth %d", halo, H_);
+  const int64_t rows = blk_.lx + 2 * halo, cols = blk_.ly + 2 * halo;
+  const float* from = q_ - int64_t(halo) * L_.pitch - halo;
+  if (on_gpu()) {
+    HIP_CHECK(hipMemcpy2DAsync(host, size_t(host_pitch) * 4, from, size_t(L_.pitch) * 4,
+                               size_t(cols) * 4, size_t(rows), hipMemcpyDeviceToHost, s_comp_));
+    HIP_CHECK(hipStreamSynchronize(s_comp_));
+  } else {
+    for (int64_t r = 0; r < rows; ++r)
+      std::memcpy(host + r * host_pitch, from + r * L_.pitch, size_t(cols) * 4);
+  }
 }
 
 void Solver::scatter_root(const float* full, int64_t step) {

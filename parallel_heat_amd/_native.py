@@ -56,6 +56,12 @@ class HeatParams(Structure):
     ]
 
 
+class HeatParamsExt(Structure):
+    """Options added after HeatParams was frozen (heat_solver_create_ex);
+    `size` is the struct's size as this package knows it."""
+    _fields_ = [("size", c_int32), ("source", c_int32)]
+
+
 SENDRECV_CB = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_int)
 ALLREDUCE_CB = ctypes.CFUNCTYPE(c_int, c_void_p, c_void_p, c_int, c_int)
 BARRIER_CB = ctypes.CFUNCTYPE(c_int, c_void_p)
@@ -129,6 +135,13 @@ class HeatRefinePlan(Structure):
                 ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32)]
 
 
+class HeatSourcePlan(Structure):
+    _fields_ = [("strips", c_int64), ("chunks", c_int64), ("units", c_int64),
+                ("chunk_rows", c_int32), ("waves", c_int32), ("align", c_int32),
+                ("vector_rows", c_int32), ("strip_cols", c_int32), ("max_chunk_rows", c_int32),
+                ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32)]
+
+
 class HeatChecksum(Structure):
     _fields_ = [("hash", c_uint64), ("sum", c_double), ("min", c_double), ("max", c_double),
                 ("count", c_int64)]
@@ -146,6 +159,20 @@ _SIGS = {
     "heat_transport_destroy": (c_int, [c_void_p]),
     "heat_transport_info_get": (c_int, [c_void_p, POINTER(HeatTransportInfo)]),
     "heat_solver_create_shared": (c_int, [POINTER(HeatParams), c_void_p, POINTER(c_void_p)]),
+    "heat_solver_create_ex": (c_int, [POINTER(HeatParams), POINTER(HeatParamsExt),
+                                      POINTER(HeatComm), POINTER(c_void_p)]),
+    "heat_solver_create_shared_ex": (c_int, [POINTER(HeatParams), POINTER(HeatParamsExt), c_void_p,
+                                             POINTER(c_void_p)]),
+    "heat_solver_set_source": (c_int, [c_void_p, c_void_p] + [c_int64] * 4 + [c_int]),
+    "heat_solver_copy_source": (c_int, [c_void_p, c_void_p, c_int64, c_int]),
+    "heat_op_source_step": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 5
+                            + [c_float, c_float] + [c_int64] * 4 + [c_void_p] * 3),
+    "heat_cpu_source_step": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 5
+                             + [c_float, c_float] + [c_int64] * 4 + [POINTER(c_float)]),
+    "heat_op_source_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 5
+                            + [POINTER(HeatSourcePlan)]),
+    "heat_op_source_max_waves": (c_int, [c_int]),
+    "heat_op_source_nontemporal": (c_int, [c_int]),
     "heat_solver_run": (c_int, [c_void_p, c_int64, POINTER(HeatRunStats)]),
     "heat_solver_enqueue": (c_int, [c_void_p, c_int64, POINTER(HeatRunStats)]),
     "heat_loopback_hub_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -370,7 +397,7 @@ def rccl_unique_id() -> bytes:
 
 __all__ = [
     "HeatParams", "HeatComm", "HeatMsg", "HeatTransportInfo", "HeatTbTuning", "HeatRunStats", "HeatBlockInfo", "HeatChecksum",
-    "HeatCoarsePlan", "HeatRefinePlan",
+    "HeatCoarsePlan", "HeatRefinePlan", "HeatParamsExt", "HeatSourcePlan",
     "SENDRECV_CB", "ALLREDUCE_CB", "BARRIER_CB", "NativeError", "lib", "call", "check",
     "available", "build_native", "loaded_path", "device_count", "rccl_unique_id",
     "require_gpu_native", "LIB_PATH", "CLI_PATH", "c_uint", "EXP_PATH", "load_exp", "unload_exp",

@@ -42,7 +42,7 @@ def build_parser() -> argparse.ArgumentParser:
     a("--eps", type=float, default=1e-3)
     a("--backend", choices=["cpu", "hip"], default=None)
     a("--threads", type=int, default=0)
-    a("--kernel", choices=["auto", "naive", "tb", "lds", "mfma"], default="auto")
+    a("--kernel", choices=["auto", "naive", "tb", "lds", "mfma", "src"], default="auto")
     a("--tb-depth", type=int, default=0)
     a("--decomp", choices=["auto", "rows", "1d", "2d"], default="auto")
     a("--px", type=int, default=0)
@@ -69,6 +69,14 @@ def build_parser() -> argparse.ArgumentParser:
            "ceil(ny/FY) values (default: ceil(nx/rows) x ceil(ny/cols))")
     a("--refine-order", type=int, choices=[0, 1], default=1,
       help="0 piecewise constant, 1 cell-centred bilinear")
+    a("--source-from", default=None, metavar="PATH",
+      help="a static heat source: a binary grid file refined onto the plate like "
+           "--init-from's; every step then adds it, u' = A u + q, with the one-step src kernel "
+           "(--kernel auto becomes src); not with --numerics mpi; checkpoints do not store it")
+    a("--source-refine", default=None, metavar="FX[xFY]",
+      help="its integer factors [ceil(nx/rows) x ceil(ny/cols)]")
+    a("--source-order", type=int, choices=[0, 1], default=1,
+      help="piecewise constant, or cell-centred bilinear")
     a("--naming", choices=["plain", "mpi", "cuda"], default="plain")
     a("--dump-initial", action="store_true")
     a("--compat", choices=["none", "mpi", "cuda"], default=None)
@@ -172,6 +180,26 @@ def main(argv=None) -> int:
                                        args.ny)
         except (ValueError, _native.NativeError) as e:
             parser.error(f"--init-from: {e}" if not str(e).startswith("--refine") else str(e))
+    source = None
+    if args.source_refine is not None and args.source_from is None:
+        parser.error("--source-refine needs --source-from PATH")
+    if args.source_from is not None:
+        if args.numerics != "fp32":
+            parser.error("--source-from needs --numerics fp32: the source step evaluates the "
+                         "canonical fp32 expression only")
+        if args.kernel not in ("auto", "src"):
+            parser.error(f"--source-from runs the src kernel: --kernel {args.kernel} has no "
+                         "source term")
+        try:
+            refine = (None if args.source_refine is None
+                      else parse_coarse(args.source_refine, "--source-refine"))
+            source = load_init_from(args.source_from, refine, args.source_order, args.nx, args.ny)
+        except (ValueError, _native.NativeError) as e:
+            parser.error(f"--source-from: {e}" if not str(e).startswith("--source-refine")
+                         else str(e))
+    elif args.kernel == "src":
+        parser.error("--kernel src is the kernel of a run with a heat source: it needs "
+                     "--source-from PATH")
     if args.gpus > 0 or args.plan:
         # Single-process native modes: the `heat` binary owns the threads
         # and the planner; same flags, same output.
@@ -185,13 +213,14 @@ def main(argv=None) -> int:
     compat = args.compat or {"mpi": "mpi", "cuda": "cuda"}.get(args.naming, "none")
     cfg = HeatConfig(nx=args.nx, ny=args.ny, steps=args.steps, cx=args.cx, cy=args.cy,
                      converge=args.converge, check_interval=args.check_interval, eps=args.eps,
-                     init=args.init, seed=args.seed, backend=backend, kernel=args.kernel,
+                     init=args.init, seed=args.seed, backend=backend,
+                     kernel="src" if source is not None else args.kernel,
                      tb_depth=args.tb_depth, threads=args.threads, decomp=args.decomp,
                      px=args.px, py=args.py, use_graph=not args.no_graph,
                      overlap=not args.no_overlap, compat=compat, schedule=args.schedule,
                      halo_passes=args.halo_passes, numerics=args.numerics,
                      phase_timing=args.phase_timing, insulated=args.insulated,
-                     periodic=args.periodic)
+                     periodic=args.periodic, source=source is not None)
     info = pcomm.init_distributed("nccl" if backend == "hip" else "gloo")
     root = info.is_root
     out = sys.stdout
@@ -202,6 +231,8 @@ def main(argv=None) -> int:
         import os
         os.environ["MASTER_PORT"] = str(args.port - 1)  # make_comm uses MASTER_PORT + 1
     solver = HeatSolver(cfg, transport=args.transport, dist_info=info)
+    if source is not None:
+        solver.set_source(source[0], source[1], source[2], order=args.source_order)
     if args.resume:
         solver.load(args.resume)
 
@@ -303,7 +334,11 @@ def main(argv=None) -> int:
                 **({"init_from": {"path": args.init_from, "rows": int(init_from[0].shape[0]),
                                   "cols": int(init_from[0].shape[1]), "fx": init_from[1],
                                   "fy": init_from[2], "order": args.refine_order}}
-                   if init_from is not None else {})) + "\n")
+                   if init_from is not None else {}),
+                **({"source": {"path": args.source_from, "rows": int(source[0].shape[0]),
+                               "cols": int(source[0].shape[1]), "fx": source[1],
+                               "fy": source[2], "order": args.source_order}}
+                   if source is not None else {})) + "\n")
         out.flush()
     solver.barrier()
     solver.close()

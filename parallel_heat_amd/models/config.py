@@ -6,6 +6,7 @@ Every field replaces one of the reference's compile-time macros
 """
 from __future__ import annotations
 
+import ctypes
 import dataclasses
 from dataclasses import dataclass
 from typing import Optional
@@ -14,7 +15,7 @@ from .. import _native
 
 INIT_MODES = {"ref-wrap": 0, "exact": 1, "ref64": 1, "random": 2, "zero": 3}
 BACKENDS = {"cpu": 0, "hip": 1}
-KERNELS = {"auto": 0, "naive": 1, "tb": 2, "lds": 3, "mfma": 4}
+KERNELS = {"auto": 0, "naive": 1, "tb": 2, "lds": 3, "mfma": 4, "src": 5}
 DECOMPS = {"auto": 0, "rows": 1, "1d": 1, "2d": 2}
 COMPATS = {"none": 0, "mpi": 1, "cuda": 2}
 SCHEDULES = {"auto": 0, "sync": 1, "overlap": 2, "pipeline": 3}
@@ -92,6 +93,8 @@ class HeatConfig:
     phase_timing: bool = False    # per-phase times (exchange/compute/reduce) in RunResult; eager
     insulated: str = ""           # insulated (zero-flux) plate edges: any of "nswe", or "all"
     periodic: str = ""            # periodic (wrap-around) axes: "x" (north-south), "y", or "xy"
+    source: bool = False          # the run has a per-cell heat source (HeatSolver.set_source):
+                                  # u' = stencil(u) + q, kernel "src", one step per memory pass
 
     def replace(self, **kw) -> "HeatConfig":
         return dataclasses.replace(self, **kw)
@@ -110,6 +113,15 @@ class HeatConfig:
             raise ValueError("halo_passes must be >= 0")
         parse_insulated(self.insulated)
         check_edges(self.insulated, self.periodic)
+        if self.source:
+            if self.numerics != "fp32":
+                raise ValueError(f"source=True needs numerics='fp32', not {self.numerics!r}")
+            if self.kernel not in ("auto", "src"):
+                raise ValueError(f"source=True runs the src kernel: kernel={self.kernel!r} has no "
+                                 "source term")
+        elif self.kernel == "src":
+            raise ValueError("kernel='src' is the kernel of a run with a heat source: set "
+                             "source=True")
 
     def total_steps(self) -> int:
         """Updates a full run performs (compat=mpi runs STEPS+1)."""
@@ -142,3 +154,10 @@ class HeatConfig:
         p.insulated = insulated_mask(self.insulated)
         p.periodic = periodic_mask(self.periodic)
         return p
+
+    def to_native_ext(self) -> _native.HeatParamsExt:
+        """The options heat_params does not carry (heat_solver_create_ex)."""
+        e = _native.HeatParamsExt()
+        e.size = ctypes.sizeof(_native.HeatParamsExt)
+        e.source = int(bool(self.source))
+        return e

@@ -123,16 +123,20 @@ class HeatSolver:
         self.device = device
         self.transport = transport
         params = config.to_native(device=device)
+        # The extended options go through the _ex entry points; a run without
+        # any keeps the original ones (an older library, HEAT_LIB A/Bs, has only those).
+        ext = [ctypes.byref(config.to_native_ext())] if config.source else []
+        sfx = "_ex" if ext else ""
         h = ctypes.c_void_p()
         if shared is not None:
             self._comm, self._keep = None, shared
-            _native.call("heat_solver_create_shared", ctypes.byref(params), shared.handle,
-                         ctypes.byref(h))
+            _native.call("heat_solver_create_shared" + sfx, ctypes.byref(params), *ext,
+                         shared.handle, ctypes.byref(h))
         else:
             self._comm, self._keep = pcomm.make_comm(transport, self.dist, device=max(device, 0),
                                                      hub=hub, group=group, rccl_uid=rccl_uid)
-            _native.call("heat_solver_create", ctypes.byref(params), ctypes.byref(self._comm),
-                         ctypes.byref(h))
+            _native.call("heat_solver_create" + sfx, ctypes.byref(params), *ext,
+                         ctypes.byref(self._comm), ctypes.byref(h))
         self._h = h
         self.info = self._info()
 
@@ -312,6 +316,37 @@ class HeatSolver:
         fy = -(-self.config.ny // cc) if fy is None else int(fy)
         _native.call("heat_solver_refine", self._h, S.ctypes.data, cr, cc, fx, fy, int(order),
                      int(step))
+
+    def set_source(self, S: Optional[np.ndarray], fx: Optional[int] = None,
+                   fy: Optional[int] = None, order: int = 1) -> None:
+        """Set the run's heat source (config.source=True): every step becomes
+        u' = stencil(u) + q with q = the refinement of the (CR, CC) source map
+        S, exactly as refine() would fill the plate from it (factors, orders,
+        limits and wrapping; fx = fy = 1 with order 0 is a per-cell source).
+        Each rank fills its block and its ghost ring without communication.
+        None clears the source (all +0).  The source is not part of the state:
+        reset(), refine(), load() and scatter() keep it, checkpoints do not
+        store it (a resumed run sets it again).  Not collective, but every rank
+        must pass the same S."""
+        if S is None:
+            _native.call("heat_solver_set_source", self._h, None, 0, 0, 1, 1, 0)
+            return
+        S = np.ascontiguousarray(S, dtype=np.float32)
+        if S.ndim != 2 or S.size == 0:
+            raise ValueError(f"source map shape {S.shape}: expected (rows, cols)")
+        cr, cc = S.shape
+        fx = -(-self.config.nx // cr) if fx is None else int(fx)
+        fy = -(-self.config.ny // cc) if fy is None else int(fy)
+        _native.call("heat_solver_set_source", self._h, S.ctypes.data, cr, cc, fx, fy, int(order))
+
+    def source_block(self, halo: int = 0) -> np.ndarray:
+        """This rank's block of the source field with `halo` (at most
+        info.halo) ghost rows and columns around it: (lx + 2 halo, ly + 2 halo)
+        float32.  For tests of the ghost rule."""
+        halo = int(halo)
+        a = np.empty((self.info.lx + 2 * halo, self.info.ly + 2 * halo), np.float32)
+        _native.call("heat_solver_copy_source", self._h, a.ctypes.data, a.shape[1], halo)
+        return a
 
     def save(self, path: str) -> None:
         """Binary grid / checkpoint (header + nx*ny fp32); collective."""

@@ -156,7 +156,7 @@ def _edge_pads(insulated: str, periodic: str):
     return pads
 
 
-def _edge_step(step, u, cx, cy, insulated, periodic=""):
+def _edge_step(step, u, cx, cy, insulated, periodic="", source=None):
     """One step with insulated (zero-flux) sides, the second-order mirror
     scheme, and periodic axes: the grid is padded by one cell beyond every
     insulated side with its reflection across the edge row / column
@@ -173,7 +173,11 @@ def _edge_step(step, u, cx, cy, insulated, periodic=""):
     p = np.pad(u, ((n0, n1), (0, 0)), mode=mx)
     p = np.pad(p, ((0, 0), (w0, w1)), mode=my)
     pad = ((n0, n1), (w0, w1))
-    v = step(p, cx, cy)
+    if source is None:
+        v = step(p, cx, cy)
+    else:  # the padding cells' source: that of the plate cells they stand for
+        q = np.pad(np.asarray(source, np.float32), ((n0, n1), (0, 0)), mode=mx)
+        v = step(p, cx, cy, source=np.pad(q, ((0, 0), (w0, w1)), mode=my))
     return np.ascontiguousarray(v[pad[0][0]:v.shape[0] - pad[0][1], pad[1][0]:v.shape[1] - pad[1][1]])
 
 
@@ -297,7 +301,8 @@ def refine_np(S: np.ndarray, nx: int, ny: int, fx: int, fy: int, order: int = 1,
 
 
 def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
-                insulated: str = "", periodic: str = "") -> np.ndarray:
+                insulated: str = "", periodic: str = "", *,
+                source: Optional[np.ndarray] = None) -> np.ndarray:
     """One step with the engine's default numerics, bit for bit: the
     expression of ``heat::stencil`` with the same operands in the same order,
         tx = fma(-2, c, s + n);  ty = fma(-2, c, e + w)
@@ -306,11 +311,16 @@ def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
     to float32 first, as HeatParams carries them); boundary ring unchanged,
     except along the `insulated` sides (mirror scheme, _edge_step: the same
     expression, the missing neighbour being the cell's mirror image) and the
-    `periodic` axes (the missing neighbour: the cell at the other end)."""
+    `periodic` axes (the missing neighbour: the cell at the other end).
+    `source`: a per-cell heat source q of u's shape; every cell the step
+    updates becomes (u' + q) rounded to float32, one more rounded add after the
+    expression, and a fixed cell ignores it."""
     if insulated or periodic:
-        return _edge_step(step_np_fma, u, cx, cy, insulated, periodic)
+        return _edge_step(step_np_fma, u, cx, cy, insulated, periodic, source)
     u = np.asarray(u, np.float32)
     out = u.copy()
+    if source is not None and np.shape(source) != u.shape:
+        raise ValueError(f"source shape {np.shape(source)} != grid shape {u.shape}")
     if u.shape[0] < 3 or u.shape[1] < 3:
         return out
     c = u[1:-1, 1:-1]
@@ -321,6 +331,10 @@ def step_np_fma(u: np.ndarray, cx: float = 0.1, cy: float = 0.1,
     tx = fma32(m2, c, ns)
     ty = fma32(m2, c, ew)
     out[1:-1, 1:-1] = fma32(np.float32(cy), ty, fma32(np.float32(cx), tx, c))
+    if source is not None:
+        with np.errstate(over="ignore", invalid="ignore"):
+            out[1:-1, 1:-1] = (out[1:-1, 1:-1]
+                               + np.asarray(source, np.float32)[1:-1, 1:-1]).astype(np.float32)
     return out
 
 
@@ -392,14 +406,23 @@ def run_np(nx: int, ny: int, steps: int, cx: float = 0.1, cy: float = 0.1,
            compat: str = "none", init: str = "ref-wrap", seed: int = 0,
            u0: Optional[np.ndarray] = None,
            numerics: str = "fp32", insulated: str = "",
-           periodic: str = "") -> Tuple[np.ndarray, int, int]:
+           periodic: str = "", *,
+           source: Optional[np.ndarray] = None) -> Tuple[np.ndarray, int, int]:
     """Run the model; returns (grid, steps_done, converged_at or -1).
     numerics: "fp32" (plain float32, a few ulps from the engine), "fma" (the
     engine's default numerics, exact) or "mpi" (its numerics="mpi", exact).
     insulated: the plate's insulated (zero-flux) sides, letters of "nswe" or
     "all"; periodic: its periodic axes, letters of "xy"; the residual then
-    covers their edge cells too."""
+    covers their edge cells too.  source: a full-plate per-cell heat source
+    (step_np_fma's; from refine_np for a source map), numerics "fma" only."""
     step = {"fp32": step_np, "fma": step_np_fma, "mpi": step_np_mpi}[numerics]
+    if source is not None:
+        if numerics != "fma":
+            raise ValueError("a source needs numerics='fma'")
+        q = np.ascontiguousarray(source, np.float32)
+
+        def step(u, cx, cy, insulated="", periodic=""):  # noqa: F811
+            return step_np_fma(u, cx, cy, insulated, periodic, source=q)
     u = init_grid(nx, ny, init, seed) if u0 is None else np.array(u0, np.float32)
     total = steps + 1 if compat == "mpi" else steps
     checks = set(check_points(total, check_interval, compat)) if converge else set()

@@ -4,10 +4,13 @@ from .stencil import (MAX_BOX_COPIES, Field, Gate, Geom, TbTuning, TbVariant, ch
                       lds_step, mfma_step, naive_step, pack, residual, resid_value,
                       set_tb_tuning, tb_stamps, tb_step, tb_tuning, unpack)
 from .stencil import refine, refine_axis, refine_plan, set_refine_max_waves
+from .stencil import (set_source_max_waves, set_source_nontemporal, source_plan,  # noqa: F401
+                      source_step)
 
 __all__ = ["Field", "Geom", "TbTuning", "TbVariant", "init_field", "lds_step", "mfma_step",
            "naive_step", "tb_step", "tb_stamps", "tb_tuning", "set_tb_tuning", "pack", "unpack",
            "residual", "resid_value", "fill_insulated_ghosts", "fill_edge_ghosts",
            "copy_boxes", "MAX_BOX_COPIES", "judge", "Gate", "checksum", "coarse", "coarse_dims",
            "coarse_plan", "set_coarse_max_waves", "refine", "refine_axis", "refine_plan",
-           "set_refine_max_waves"]
+           "set_refine_max_waves", "source_step", "source_plan", "set_source_max_waves",
+           "set_source_nontemporal"]

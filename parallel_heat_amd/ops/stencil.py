@@ -196,6 +196,69 @@ def lds_step(src: Field, dst: Field, geom: Geom, box: Optional[Box] = None,
                  ctypes.c_void_p(_stream()), {"fp32": 0, "mpi": 1}[numerics])
 
 
+def source_step(src: Field, dst: Field, q: Field, geom: Geom, box: Optional[Box] = None,
+                resid: Optional[torch.Tensor] = None,
+                gate: Optional[torch.Tensor] = None) -> None:
+    """One Jacobi step over `box` with a per-cell heat source: u' = stencil(u) + q
+    on every cell the step updates (one rounded fp32 add after the unchanged
+    expression; fixed cells ignore q).  q has the layout of src and dst.  The
+    streaming HIP kernel on GPU fields (`gate`: an int32 GPU tensor whose first
+    word, if non-zero, makes the launch write nothing), its host twin on CPU
+    fields.  resid: max |new - old| over the box's updated cells."""
+    r0, r1, c0, c1 = box or (0, src.lx, 0, src.ly)
+    if src.pitch != dst.pitch or src.pitch != q.pitch:
+        raise ValueError("src/dst/q layouts differ")
+    if src.device.type == "cpu":
+        if gate is not None:
+            raise ValueError("the gate is a device word: GPU fields only")
+        r = ctypes.c_float()
+        _native.call("heat_cpu_source_step", ctypes.c_void_p(src.ptr()), ctypes.c_void_p(dst.ptr()),
+                     ctypes.c_void_p(q.ptr()), src.pitch, geom.gx0, geom.gy0, geom.nx, geom.ny,
+                     geom.cx, geom.cy, r0, r1, c0, c1,
+                     ctypes.byref(r) if resid is not None else None)
+        if resid is not None:
+            old, new = resid[:1].clone(), torch.tensor([r.value], dtype=torch.float32)
+            # The word keeps the larger of the two as unsigned float bits (a NaN on top).
+            if (int(new.view(torch.int32)) & 0xFFFFFFFF) > (int(old) & 0xFFFFFFFF):
+                resid[:1] = new.view(torch.int32)
+        return
+    rp = _resid_ptr(resid)
+    if gate is not None and (gate.dtype != torch.int32 or gate.device != src.device):
+        raise ValueError("gate must be an int32 tensor on the fields' device")
+    _native.call("heat_op_source_step", ctypes.c_void_p(src.ptr()), ctypes.c_void_p(dst.ptr()),
+                 ctypes.c_void_p(q.ptr()), src.pitch, geom.gx0, geom.gy0, geom.nx, geom.ny,
+                 geom.cx, geom.cy, r0, r1, c0, c1, ctypes.c_void_p(rp) if rp else None,
+                 ctypes.c_void_p(_stream()),
+                 ctypes.c_void_p(gate.data_ptr()) if gate is not None else None)
+
+
+def source_plan(src: Field, dst: Field, q: Field, box: Optional[Box] = None) -> dict:
+    """The launch plan `source_step` takes for these GPU fields and box (strips,
+    chunks, units, chunk_rows, waves, align, vector_rows) together with the
+    planner's constants strip_cols, max_chunk_rows, min_chunk_rows and
+    waves_per_cu."""
+    r0, r1, c0, c1 = box or (0, src.lx, 0, src.ly)
+    p = _native.HeatSourcePlan()
+    _native.call("heat_op_source_plan", ctypes.c_void_p(src.ptr()), ctypes.c_void_p(dst.ptr()),
+                 ctypes.c_void_p(q.ptr()), src.pitch, r0, r1, c0, c1, ctypes.byref(p))
+    return {k: int(getattr(p, k)) for k, _ in p._fields_}
+
+
+def set_source_max_waves(waves: int) -> None:
+    """Cap the waves of a `source_step` launch (0: the default, 16 waves per
+    CU, about half the kernel's occupancy): tests make the kernel's grid-stride
+    loop run more than once with it."""
+    _native.call("heat_op_source_max_waves", int(waves))
+
+
+def set_source_nontemporal(mode: int) -> None:
+    """For tests and tools/source_bench.py only (process-global: it changes
+    every launch of every solver in the process): q loads and dst stores of
+    `source_step` non-temporal (1) or plain (0); -1 = the default, non-temporal
+    when a step sweeps more than 256 MiB."""
+    _native.call("heat_op_source_nontemporal", int(mode))
+
+
 def mfma_step(src: Field, dst: Field, geom: Geom, box: Optional[Box] = None,
               resid: Optional[torch.Tensor] = None) -> None:
     """One Jacobi step over `box` as banded matmuls on the fp32 MFMA units
