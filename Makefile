@@ -45,7 +45,7 @@ $(BUILD)/obj/tb_scalar.o $(BUILD)/obj/tb_split.o $(BUILD)/obj/tb_tile.o $(BUILD)
   $(BUILD)/obj/tb_resident_xl0.o $(BUILD)/obj/tb_resident_xl1.o $(BUILD)/obj/tb_resident_xl2.o \
   $(BUILD)/obj/tb_split_rla.o $(BUILD)/obj/tb_split_rlb.o $(BUILD)/obj/tb_split_rlc.o \
   $(BUILD)/obj/tb_split_mixed.o $(BUILD)/obj/tb_split_nt.o $(BUILD)/obj/tb_split_pk.o \
-  $(BUILD)/obj/tb_chain.o: HIPFLAGS += -fno-slp-vectorize
+  $(BUILD)/obj/tb_chain.o $(BUILD)/obj/source_tb.o: HIPFLAGS += -fno-slp-vectorize
 # The streaming split build that runs the whole-GPU plates (8192^2 and up)
 # takes LLVM's max-ILP machine scheduler: +1.5 % at 8192^2 in an interleaved
 # same-box A/B; the resident tiles keep the default scheduler (no gain there).
@@ -87,7 +87,7 @@ ASM ?= tb_split
 asm:
 	@mkdir -p $(BUILD)/asm
 	cd $(BUILD)/asm && $(HIPCC) $(patsubst -Icsrc/include,-I../../csrc/include,$(HIPFLAGS)) \
-	  $(if $(filter tb_scalar tb_split tb_tile,$(ASM)),-fno-slp-vectorize) --offload-device-only -S \
+	  $(if $(filter tb_scalar tb_split tb_tile source_tb,$(ASM)),-fno-slp-vectorize) --offload-device-only -S \
 	  -o $(ASM).s ../../csrc/kernels/$(ASM).hip
 
 # Every kernel of every unit, from the built library's code-object metadata

@@ -243,6 +243,28 @@ int heat_op_source_plan(const float* src, const float* dst, const float* q, int6
                         int64_t r0, int64_t r1, int64_t c0, int64_t c1, heat_source_plan* out);
 int heat_op_source_max_waves(int waves);
 int heat_op_source_nontemporal(int mode);
+/* k fused source steps in one launch (heat::gpu::source_tb_step), 2 <= k <= 8:
+   dst on the box is what k calls of heat_op_source_step give, call j over the box
+   grown by k-1-j and clipped to the plate; resid: the last level's.  Device only. */
+int heat_op_source_tb_step(const float* src, float* dst, const float* q, int64_t pitch,
+                           int64_t gx0, int64_t gy0, int64_t nx, int64_t ny, float cx, float cy,
+                           int64_t r0, int64_t r1, int64_t c0, int64_t c1, int k, unsigned* resid,
+                           void* stream, const unsigned* gate);
+/* Its launch plan (heat::gpu::source_tb_plan) with the planner's constants, and a
+   cap on the waves of a launch (0 = default; process-global, for tests).  With a
+   cap set the plan needs no device: it depends on the addresses' alignment only. */
+typedef struct heat_source_tb_plan_t {
+  int64_t strips, chunks, units;
+  int32_t chunk_rows, waves, align, vector_rows, overlap, strip_stride;
+  int32_t strip_cols, max_chunk_rows, min_chunk_rows, waves_per_cu, max_depth; /* constants */
+  int32_t pad_;
+} heat_source_tb_plan_t;
+int heat_source_tb_plan(const float* src, const float* dst, const float* q, int64_t pitch,
+                        int64_t r0, int64_t r1, int64_t c0, int64_t c1, int k,
+                        heat_source_tb_plan_t* out);
+int heat_source_tb_set_max_waves(int waves);
+/* Fused launches this process has enqueued so far (solvers' and heat_op_source_tb_step's). */
+int64_t heat_source_tb_launches(void);
 // Diagnostics: per-wave start/end clock stamps of subsequent TB launches
 // (4 u64 per wave: start, end at 100 MHz, block, strip<<32|chunk); null = off.
 int heat_op_tb_stamps(void* buf, int64_t waves);

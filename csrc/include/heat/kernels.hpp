@@ -417,6 +417,50 @@ void source_set_max_waves(int waves);
 // above the Infinity Cache's 256 MiB (profiles/source.md).
 void source_set_nontemporal(int mode);
 
+// k fused source steps in one launch (source_tb.hip), 2 <= k <=
+// kSourceTbMaxDepth: dst on `box` is bit for bit what k calls of source_step
+// give, call j = 0 .. k-1 over `box` grown by k-1-j on every side and clipped
+// to the plate rectangle of g; src and dst must not alias and src is left
+// untouched.  Cells of a fixed edge and cells off the plate keep their centre
+// value at every level.  Reads src only in `box` grown by k and q only in
+// `box` grown by k-1, both clipped to the plate; writes dst on `box` alone.
+// With resid: max |u_k - u_{k-1}| over the updated cells of `box` (the last
+// level only), as float bits with a NaN on top, one atomic per workgroup.  A
+// closed g.gate writes nothing.  Any 4-byte-aligned pointers and any pitch >=
+// the box's width (dword accesses unless the pitch is a multiple of 4 and the
+// arrays share their 16-byte phase).  Two LDS words, no scratch;
+// graph-capturable, no host synchronisation.
+constexpr int kSourceTbMaxDepth = 8;
+void source_tb_step(const float* src, float* dst, const float* q, const StencilGeom& g,
+                    const Box& box, int k, unsigned* resid, hipStream_t st);
+// The launch plan of source_tb_step.  A unit is one wave's share: a strip of
+// kSourceTbStripCols columns, of which it stores the middle strip_stride =
+// kSourceTbStripCols - 2 overlap (overlap = round_up(k, 4): neighbouring
+// strips share that many columns per side, lane 0 of strip 0 starts `align` +
+// overlap columns left of the box), times a chunk of chunk_rows rows, streamed
+// with the k levels' row windows and a ring of k rows of q in registers (k
+// more rows of src above and below the chunk).
+constexpr int kSourceTbStripCols = 256;     // 64 lanes x float4
+constexpr int kSourceTbMaxChunkRows = 256;  // 2k of chunk_rows + 2k streamed rows are redundant;
+constexpr int kSourceTbMinChunkRows = 32;   // shortened while the units do not fill a round
+constexpr int kSourceTbWavesPerCu = 8;      // launch size: two waves per SIMD
+struct SourceTbPlan {
+  int64_t strips = 0, chunks = 0, units = 0;
+  int chunk_rows = 0;
+  int waves = 0;         // waves launched
+  int align = 0;         // columns between the 16-byte boundary and box.c0
+  int overlap = 0;       // round_up(k, 4)
+  int strip_stride = 0;  // columns a strip stores
+  bool vector_rows = false;
+};
+SourceTbPlan source_tb_plan(const float* src, const float* dst, const float* q, int64_t pitch,
+                            const Box& box, int k);
+// Tests: cap the waves of a launch (0: kSourceTbWavesPerCu per CU, at most the
+// kernel's resident waves).  With a cap the plan needs no device.
+void source_tb_set_max_waves(int waves);
+// Fused launches enqueued by this process so far (tests: which kernel ran).
+long long source_tb_launches();
+
 // Device-side convergence decision (one per check, stream-ordered after the
 // residual of the check's pass and its all-reduce): the host never waits on a
 // check.  Unless the gate is already closed, judge_check compares the

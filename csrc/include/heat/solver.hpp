@@ -322,6 +322,7 @@ class Solver {
   bool warmed_ = false;    // RCCL connections established outside capture
   bool resident_ = false;  // resident-tile launches enabled for this solver
   bool chain_ = false;     // chained level-split passes (HEAT_TB_CHAIN=1; off by default)
+  bool src_fused_ = true;  // source passes of depth >= 2 in fused launches (HEAT_SRC_FUSED=0: off)
   bool resident_force_ = false;  // HEAT_TB_RESIDENT=2: also with ranks sharing the device
   bool resident_used_ = false;  // one was enqueued in this run (check its error word)
   bool pending_ = false;         // an enqueue()d run not yet completed by run()

@@ -622,6 +622,47 @@ int heat_op_source_nontemporal(int mode) {
   return guard([&] { heat::gpu::source_set_nontemporal(mode); });
 }
 
+int heat_op_source_tb_step(const float* src, float* dst, const float* q, int64_t pitch,
+                           int64_t gx0, int64_t gy0, int64_t nx, int64_t ny, float cx, float cy,
+                           int64_t r0, int64_t r1, int64_t c0, int64_t c1, int k, unsigned* resid,
+                           void* stream, const unsigned* gate) {
+  return guard([&] {
+    auto g = geom(pitch, gx0, gy0, nx, ny, cx, cy);
+    g.gate = gate;
+    heat::gpu::source_tb_step(src, dst, q, g, heat::Box{r0, r1, c0, c1}, k, resid, S(stream));
+  });
+}
+
+int heat_source_tb_plan(const float* src, const float* dst, const float* q, int64_t pitch,
+                        int64_t r0, int64_t r1, int64_t c0, int64_t c1, int k,
+                        heat_source_tb_plan_t* out) {
+  return guard([&] {
+    const heat::gpu::SourceTbPlan p =
+        heat::gpu::source_tb_plan(src, dst, q, pitch, heat::Box{r0, r1, c0, c1}, k);
+    std::memset(out, 0, sizeof *out);
+    out->strips = p.strips;
+    out->chunks = p.chunks;
+    out->units = p.units;
+    out->chunk_rows = p.chunk_rows;
+    out->waves = p.waves;
+    out->align = p.align;
+    out->vector_rows = p.vector_rows;
+    out->overlap = p.overlap;
+    out->strip_stride = p.strip_stride;
+    out->strip_cols = heat::gpu::kSourceTbStripCols;
+    out->max_chunk_rows = heat::gpu::kSourceTbMaxChunkRows;
+    out->min_chunk_rows = heat::gpu::kSourceTbMinChunkRows;
+    out->waves_per_cu = heat::gpu::kSourceTbWavesPerCu;
+    out->max_depth = heat::gpu::kSourceTbMaxDepth;
+  });
+}
+
+int heat_source_tb_set_max_waves(int waves) {
+  return guard([&] { heat::gpu::source_tb_set_max_waves(waves); });
+}
+
+int64_t heat_source_tb_launches(void) { return heat::gpu::source_tb_launches(); }
+
 int heat_op_mfma_step(const float* src, float* dst, int64_t pitch, int64_t gx0, int64_t gy0,
                       int64_t nx, int64_t ny, float cx, float cy, int64_t r0, int64_t r1,
                       int64_t c0, int64_t c1, unsigned* resid, void* stream) {

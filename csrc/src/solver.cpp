@@ -236,6 +236,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   // Tests: this rank's first run with resident spans reports a give-up.
   inject_giveup_ = resident_ && env_int("HEAT_TEST_RES_GIVEUP_RANK", -1) == tr_->rank();
   host_checks_ = env_int("HEAT_HOST_CHECKS", 0) != 0;
+  src_fused_ = env_int("HEAT_SRC_FUSED", 1) != 0;
   timing_ = P_.phase_timing || env_int("HEAT_PHASE_TIMING", 0) != 0;
   // Waits on the device poll the transport and give up after this long
   // without completion (multi-rank GPU runs; wait_event).
@@ -763,15 +764,23 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
   const Box own{on ? -er : 0, lx + (os ? er : 0), ow ? -ec : 0, ly + (oe ? ec : 0)};
 
   if (!tb_kernel()) {
-    // k single steps over shrinking regions (deep halo), ping-ponging.
-    for (int j = 0; j < k; ++j) {
-      const int64_t e = k - 1 - j;
+    // k single steps over shrinking regions (deep halo), ping-ponging.  With
+    // a heat source the steps go in groups of up to kSourceTbMaxDepth, one
+    // fused launch and one flip of cur_ each; a group ends at step rl, so that
+    // the residual is its last level's.
+    const bool fused = P_.kernel == KernelKind::Source && src_fused_;
+    for (int j = 0; j < k;) {
+      const int end = j < rl ? rl : k;
+      const int n = fused ? std::min(end - j, gpu::kSourceTbMaxDepth) : 1;
+      const int64_t e = k - j - n;  // the steps still to come
       Box b{on ? own.r0 - e : 0, own.r1 + (os ? e : 0), ow ? own.c0 - e : 0,
             own.c1 + (oe ? e : 0)};
       const float* a = field_[cur_];
       float* d = field_[cur_ ^ 1];
-      unsigned* rj = j == rl - 1 ? r : nullptr;
-      if (P_.kernel == KernelKind::Source)
+      unsigned* rj = j + n == rl ? r : nullptr;
+      if (n > 1)
+        gpu::source_tb_step(a, d, q_, g, b, n, rj, st);
+      else if (P_.kernel == KernelKind::Source)
         gpu::source_step(a, d, q_, g, b, rj, st);
       else if (P_.kernel == KernelKind::Lds)
         gpu::lds_step(a, d, g, b, rj, st);
@@ -780,6 +789,7 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
       else
         gpu::naive_step(a, d, g, b, rj, st);
       cur_ ^= 1;
+      j += n;
     }
     return;
   }

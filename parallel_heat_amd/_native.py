@@ -142,6 +142,15 @@ class HeatSourcePlan(Structure):
                 ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32)]
 
 
+class HeatSourceTbPlan(Structure):
+    _fields_ = [("strips", c_int64), ("chunks", c_int64), ("units", c_int64),
+                ("chunk_rows", c_int32), ("waves", c_int32), ("align", c_int32),
+                ("vector_rows", c_int32), ("overlap", c_int32), ("strip_stride", c_int32),
+                ("strip_cols", c_int32), ("max_chunk_rows", c_int32),
+                ("min_chunk_rows", c_int32), ("waves_per_cu", c_int32), ("max_depth", c_int32),
+                ("pad_", c_int32)]
+
+
 class HeatChecksum(Structure):
     _fields_ = [("hash", c_uint64), ("sum", c_double), ("min", c_double), ("max", c_double),
                 ("count", c_int64)]
@@ -173,6 +182,12 @@ _SIGS = {
                             + [POINTER(HeatSourcePlan)]),
     "heat_op_source_max_waves": (c_int, [c_int]),
     "heat_op_source_nontemporal": (c_int, [c_int]),
+    "heat_op_source_tb_step": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 5
+                               + [c_float, c_float] + [c_int64] * 4 + [c_int] + [c_void_p] * 3),
+    "heat_source_tb_plan": (c_int, [c_void_p, c_void_p, c_void_p] + [c_int64] * 5 + [c_int]
+                            + [POINTER(HeatSourceTbPlan)]),
+    "heat_source_tb_set_max_waves": (c_int, [c_int]),
+    "heat_source_tb_launches": (c_int64, []),
     "heat_solver_run": (c_int, [c_void_p, c_int64, POINTER(HeatRunStats)]),
     "heat_solver_enqueue": (c_int, [c_void_p, c_int64, POINTER(HeatRunStats)]),
     "heat_loopback_hub_create": (c_int, [c_int, POINTER(c_void_p)]),
@@ -370,6 +385,16 @@ def call(name: str, *args):
         raise NativeError(f"{LIB_PATH} has no entry point {name}: it is older than this package; "
                           "rebuild it with `make`")
     check(fn(*args))
+
+
+def source_tb_launches() -> int:
+    """Fused source launches (`heat_op_source_tb_step`, and a solver's passes)
+    this process has enqueued so far."""
+    fn = getattr(lib(), "heat_source_tb_launches", None)
+    if fn is None:
+        raise NativeError(f"{LIB_PATH} has no entry point heat_source_tb_launches: it is older "
+                          "than this package; rebuild it with `make`")
+    return int(fn())
 
 
 def loaded_path() -> str:

@@ -6,6 +6,8 @@ from .stencil import (MAX_BOX_COPIES, Field, Gate, Geom, TbTuning, TbVariant, ch
 from .stencil import refine, refine_axis, refine_plan, set_refine_max_waves
 from .stencil import (set_source_max_waves, set_source_nontemporal, source_plan,  # noqa: F401
                       source_step)
+from .stencil import (set_source_tb_max_waves, source_tb_launches, source_tb_plan,  # noqa: F401
+                      source_tb_step)
 
 __all__ = ["Field", "Geom", "TbTuning", "TbVariant", "init_field", "lds_step", "mfma_step",
            "naive_step", "tb_step", "tb_stamps", "tb_tuning", "set_tb_tuning", "pack", "unpack",
@@ -13,4 +15,5 @@ __all__ = ["Field", "Geom", "TbTuning", "TbVariant", "init_field", "lds_step", "
            "copy_boxes", "MAX_BOX_COPIES", "judge", "Gate", "checksum", "coarse", "coarse_dims",
            "coarse_plan", "set_coarse_max_waves", "refine", "refine_axis", "refine_plan",
            "set_refine_max_waves", "source_step", "source_plan", "set_source_max_waves",
-           "set_source_nontemporal"]
+           "set_source_nontemporal", "source_tb_step", "source_tb_plan",
+           "set_source_tb_max_waves", "source_tb_launches"]

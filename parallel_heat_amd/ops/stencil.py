@@ -259,6 +259,52 @@ def set_source_nontemporal(mode: int) -> None:
     _native.call("heat_op_source_nontemporal", int(mode))
 
 
+def source_tb_step(src: Field, dst: Field, q: Field, geom: Geom, box: Optional[Box], k: int,
+                   resid: Optional[torch.Tensor] = None,
+                   gate: Optional[torch.Tensor] = None) -> None:
+    """k fused source steps in one launch (GPU only, 2 <= k <= 8): dst on `box`
+    is bit for bit what k calls of `source_step` give, call j over `box` grown
+    by k-1-j on every side and clipped to the plate.  Reads src in `box` grown
+    by k and q in `box` grown by k-1 (clipped to the plate), writes dst on
+    `box` alone.  resid: max |u_k - u_(k-1)| over the box's updated cells."""
+    r0, r1, c0, c1 = box or (0, src.lx, 0, src.ly)
+    if src.pitch != dst.pitch or src.pitch != q.pitch:
+        raise ValueError("src/dst/q layouts differ")
+    if src.device.type != "cuda":
+        raise ValueError("source_tb_step needs GPU fields")
+    rp = _resid_ptr(resid)
+    if gate is not None and (gate.dtype != torch.int32 or gate.device != src.device):
+        raise ValueError("gate must be an int32 tensor on the fields' device")
+    _native.call("heat_op_source_tb_step", ctypes.c_void_p(src.ptr()),
+                 ctypes.c_void_p(dst.ptr()), ctypes.c_void_p(q.ptr()), src.pitch, geom.gx0,
+                 geom.gy0, geom.nx, geom.ny, geom.cx, geom.cy, r0, r1, c0, c1, int(k),
+                 ctypes.c_void_p(rp) if rp else None, ctypes.c_void_p(_stream()),
+                 ctypes.c_void_p(gate.data_ptr()) if gate is not None else None)
+
+
+def source_tb_plan(src: Field, dst: Field, q: Field, box: Optional[Box], k: int) -> dict:
+    """The launch plan `source_tb_step` takes for these fields, box and depth
+    (strips, chunks, units, chunk_rows, waves, align, vector_rows, overlap,
+    strip_stride) with the planner's constants.  Only the fields' addresses and
+    pitch matter: with `set_source_tb_max_waves` set it needs no GPU."""
+    r0, r1, c0, c1 = box or (0, src.lx, 0, src.ly)
+    p = _native.HeatSourceTbPlan()
+    _native.call("heat_source_tb_plan", ctypes.c_void_p(src.ptr()), ctypes.c_void_p(dst.ptr()),
+                 ctypes.c_void_p(q.ptr()), src.pitch, r0, r1, c0, c1, int(k), ctypes.byref(p))
+    return {name: int(getattr(p, name)) for name, _ in p._fields_ if name != "pad_"}
+
+
+def set_source_tb_max_waves(waves: int) -> None:
+    """Cap the waves of a `source_tb_step` launch (0: the default, 8 waves per
+    CU): tests make the kernel's loop over units run more than once with it."""
+    _native.call("heat_source_tb_set_max_waves", int(waves))
+
+
+def source_tb_launches() -> int:
+    """Fused source launches this process has enqueued so far."""
+    return _native.source_tb_launches()
+
+
 def mfma_step(src: Field, dst: Field, geom: Geom, box: Optional[Box] = None,
               resid: Optional[torch.Tensor] = None) -> None:
     """One Jacobi step over `box` as banded matmuls on the fp32 MFMA units
