@@ -18,6 +18,21 @@ struct Geom {
   float cx = 0.1f, cy = 0.1f;
   int numerics = 0;  // heat::Numerics
 };
+// The same geometry from a struct with fields of these names (the solver's
+// gpu::StencilGeom, which this header does not see), field by field.
+template <class G>
+Geom geom_of(const G& s) {
+  Geom g;
+  g.pitch = s.pitch;
+  g.gx0 = s.gx0;
+  g.gy0 = s.gy0;
+  g.nx = s.nx;
+  g.ny = s.ny;
+  g.cx = s.cx;
+  g.cy = s.cy;
+  g.numerics = s.numerics;
+  return g;
+}
 
 void set_threads(int n);
 int get_threads();

@@ -2,24 +2,97 @@
 // which passes-per-exchange m keeps every rank's resident span box inside a
 // one-dispatch-round resident tile plan of the same shape as its owned
 // block's.  Separate from topology.hpp so the kernel units, which include
-// that header, do not depend on it.
+// that header, do not depend on it (tb_resident.hip alone includes this one,
+// for the resident shapes below).
+//
+// Also the geometry of a pass, shared by the solver, the planner and `heat
+// --plan`: which cells a pass of depth k computes and which ghosts stay valid.
 #pragma once
 
 #include <functional>
+#include <utility>
 
 #include "heat/topology.hpp"
 
 namespace heat {
 
+// The sides and axes of one rank.  open[d]: side d has ghosts to keep: a
+// neighbour rank, or the rank's own insulated or periodic plate edge (a rank
+// without a neighbour on a side is at the plate edge there).  ns, ew: the axis
+// is decomposed, has an insulated side or is periodic; from global quantities
+// only, so every rank agrees.  An open side lies on an active axis.
+struct Sides {
+  bool open[4] = {false, false, false, false};
+  bool ns = false, ew = false;
+};
+Sides make_sides(const Cart& cart, const Block& b, unsigned insulated, unsigned periodic);
+
+// The lx x ly owned block grown by er rows and ec columns into the ghost ring
+// on every open side: the box of a deep-halo pass.
+inline Box grown_box(int64_t lx, int64_t ly, const Sides& s, int64_t er, int64_t ec) {
+  return Box{s.open[North] ? -er : 0, lx + (s.open[South] ? er : 0), s.open[West] ? -ec : 0,
+             ly + (s.open[East] ? ec : 0)};
+}
+
+// gr, gc: how many ghost rows/columns of the current field hold the current
+// time level.  A k-step pass needs k; an exchange refills H.  Invariant: they
+// never exceed the depth of the last exchange of this buffer -- N/S row
+// messages carry the sender's own (stale) ghost columns into our corners, and
+// only the corner unpack of THAT exchange overwrites them up to its depth (the
+// overlap schedule exchanges k < H and then claims 0;
+// tests/test_gpu_loopback.py::test_loopback_deep_halo_chunked mixes depths and
+// short tail segments on 2 x 2 ranks).  The pass then also updates the
+// (valid - k) ghost rows/columns next to the block, which become the valid
+// ghosts of the next level.  Only active axes count, so every rank makes the
+// same decision.
+struct GhostState {
+  int64_t gr = 0, gc = 0;
+  bool needs_exchange(const Sides& s, int k) const { return (s.ns && gr < k) || (s.ew && gc < k); }
+  void refill(int64_t H) { gr = gc = H; }
+  // A k-step pass: returns the growth (er, ec) of its box and leaves the
+  // validity after it.  `tb`: TB boxes start on a float4 column, so the column
+  // extension is rounded down to a multiple of 4.
+  std::pair<int64_t, int64_t> advance(const Sides& s, int k, bool tb) {
+    gr = s.ns ? gr - k : 0;
+    gc = s.ew ? (tb ? (gc - k) / 4 * 4 : gc - k) : 0;
+    return {gr, gc};
+  }
+};
+
 // The first box of a resident span after an exchange of H = m * depth deep
-// halos: rank b's owned block grown by H - depth rows (columns: rounded down
-// to 4) on every side with a neighbour along a decomposed axis, as
-// Solver::resident_span tracks ghost validity.  `insulated`
-// (Params::insulated): an insulated plate edge counts as a neighbour, and an
-// axis with one as decomposed.  `periodic` (Params::periodic): both sides of a
-// periodic axis count as neighbours, and the axis as decomposed.
+// halos: rank b's owned block after refill(H) and advance(depth) of the TB
+// kernels.
 Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated = 0,
              unsigned periodic = 0);
+
+// One launch of a k-step pass run by kernels that take fewer than k steps: n
+// steps over the pass's box grown by `grow`, the steps still to come behind
+// it; takes_resid: it ends at the pass's check level.
+struct SubPass {
+  int n = 0, grow = 0;
+  bool takes_resid = false;
+};
+// The launch that starts at step j of the pass (j = 0, then j += n up to k):
+// at most group_max steps, and none past step rl when rl > j.
+inline SubPass sub_pass(int k, int rl, int group_max, int j) {
+  const int left = (j < rl ? rl : k) - j, n = left < group_max ? left : group_max;
+  return {n, k - j - n, j + n == rl};
+}
+// The first steps of a pass again, `left` of them still to run: the depth of
+// the next launch.  All at once if the kernel takes that depth (`supported`),
+// else left mod 8 first, then 8s.
+inline int replay_depth(int left, bool supported) {
+  return supported ? left : (left % 8 != 0 ? left % 8 : 8);
+}
+
+// The overlap schedules' split of the owned block: an interior that needs no
+// ghosts, `band` away from every side with a neighbour rank (column cuts on
+// float4 columns; empty: no split), and the boundary bands around it: top,
+// bottom, left, right.
+struct InteriorSplit {
+  Box interior, bands[4];
+};
+InteriorSplit interior_split(int64_t lx, int64_t ly, const std::array<int, 4>& nbr, int64_t band);
 
 // A resident tile plan's shape as one int: rows per wave << 8 | waves per
 // workgroup (0: the box has no one-round resident plan).

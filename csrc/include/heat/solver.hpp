@@ -48,6 +48,7 @@
 #include "heat/io.hpp"
 #include "heat/kernels.hpp"
 #include "heat/params.hpp"
+#include "heat/plan.hpp"
 #include "heat/topology.hpp"
 #include "heat/transport.hpp"
 
@@ -291,19 +292,6 @@ class Solver {
   // with one rank along the axis, this rank's own opposite edge.
   bool periodic(int dir) const { return (periodic_sides(P_.periodic) >> dir) & 1; }
   bool edge_ghosts() const { return P_.insulated != 0 || P_.periodic != 0; }
-  // The side has ghosts to keep: a neighbour rank, or this rank's own
-  // insulated or periodic plate edge (a rank without a neighbour on a side is
-  // at the plate edge there).
-  bool open_side(int dir) const {
-    return blk_.nbr[size_t(dir)] >= 0 || insulated(dir) || periodic(dir);
-  }
-  // Axis-level decisions, from global quantities only (every rank agrees).
-  bool ns_active() const {
-    return cart_.px > 1 || (P_.insulated & 3) != 0 || (P_.periodic & kPeriodicX) != 0;
-  }
-  bool ew_active() const {
-    return cart_.py > 1 || (P_.insulated & 12) != 0 || (P_.periodic & kPeriodicY) != 0;
-  }
   // This rank's locally wrapped axes (Params::periodic bits): periodic, and
   // spanned by this rank alone.
   int fill_axes() const;
@@ -334,7 +322,8 @@ class Solver {
   bool watch_ = false;     // multi-rank GPU run: waits poll with a watchdog
   double watchdog_s_ = 300.0;
   std::atomic<bool> aborted_{false};
-  int64_t gr_ = 0, gc_ = 0;  // ghost rows/columns of field_[cur_] at the current level
+  Sides sides_;    // open sides and active axes of this rank (plan.hpp)
+  GhostState gh_;  // ghost rows/columns of field_[cur_] at the current level
   bool comm_pending_ = false;  // comm stream has unjoined work
   int cur_ = 0;
   int64_t step_ = 0;

@@ -84,6 +84,7 @@ Solver::Solver(const Params& p, std::shared_ptr<Transport> tr)
   }
   cart_ = Cart(tr_->world(), P_.decomp, P_.px, P_.py, P_.nx, P_.ny);
   blk_ = make_block(cart_, tr_->rank(), P_.nx, P_.ny, P_.periodic);
+  sides_ = make_sides(cart_, blk_, P_.insulated, P_.periodic);
   if (on_gpu()) {
     // The TB kernel evaluates the canonical fp32 expression only.
     if (P_.numerics != Numerics::Fp32) {
@@ -424,7 +425,7 @@ void Solver::init_fields() {
   if (on_gpu()) HIP_CHECK(hipStreamSynchronize(s_comp_));
   cur_ = 0;
   step_ = 0;
-  gr_ = gc_ = 0;
+  gh_ = {};
 }
 
 void Solver::reset() {
@@ -754,14 +755,7 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
   float* dst = field_[cur_ ^ 1];
   const gpu::StencilGeom g = geom();
   unsigned* r = rl > 0 ? d_resid_ : nullptr;
-  const int64_t lx = blk_.lx, ly = blk_.ly;
-  const auto& nb = blk_.nbr;
   const int waves_target = gpu::tb_tuning().waves;
-  // The box of this pass: the owned block grown by (er, ec) into the ghost
-  // ring on sides that have a neighbour or are insulated (deep-halo passes).
-  const bool on = open_side(North), os = open_side(South), ow = open_side(West),
-             oe = open_side(East);
-  const Box own{on ? -er : 0, lx + (os ? er : 0), ow ? -ec : 0, ly + (oe ? ec : 0)};
 
   if (!tb_kernel()) {
     // k single steps over shrinking regions (deep halo), ping-ponging.  With
@@ -770,16 +764,13 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
     // the residual is its last level's.
     const bool fused = P_.kernel == KernelKind::Source && src_fused_;
     for (int j = 0; j < k;) {
-      const int end = j < rl ? rl : k;
-      const int n = fused ? std::min(end - j, gpu::kSourceTbMaxDepth) : 1;
-      const int64_t e = k - j - n;  // the steps still to come
-      Box b{on ? own.r0 - e : 0, own.r1 + (os ? e : 0), ow ? own.c0 - e : 0,
-            own.c1 + (oe ? e : 0)};
+      const SubPass sp = sub_pass(k, rl, fused ? gpu::kSourceTbMaxDepth : 1, j);
+      const Box b = grown_box(blk_.lx, blk_.ly, sides_, er + sp.grow, ec + sp.grow);
       const float* a = field_[cur_];
       float* d = field_[cur_ ^ 1];
-      unsigned* rj = j + n == rl ? r : nullptr;
-      if (n > 1)
-        gpu::source_tb_step(a, d, q_, g, b, n, rj, st);
+      unsigned* rj = sp.takes_resid ? r : nullptr;
+      if (sp.n > 1)
+        gpu::source_tb_step(a, d, q_, g, b, sp.n, rj, st);
       else if (P_.kernel == KernelKind::Source)
         gpu::source_step(a, d, q_, g, b, rj, st);
       else if (P_.kernel == KernelKind::Lds)
@@ -789,28 +780,26 @@ void Solver::compute_gpu(int k, int rl, bool split, int part, int band, int64_t 
       else
         gpu::naive_step(a, d, g, b, rj, st);
       cur_ ^= 1;
-      j += n;
+      j += sp.n;
     }
     return;
   }
 
   if (!split) {
+    // The box of this pass: the owned block grown by (er, ec) into the ghost
+    // ring on its open sides (deep-halo passes).
+    const Box own = grown_box(blk_.lx, blk_.ly, sides_, er, ec);
     gpu::tb_step(src, dst, g, &own, 1, k, r, st, waves_target, -1, rl);
     return;
   }
   // Boundary bands are `band` >= k deep (k for exchange-first; H for the
   // boundary-first pipeline, whose next exchange sends H rows/columns that
   // the concurrent interior launch must not write).
-  if (band < k) band = k;
-  const int64_t r0 = nb[North] >= 0 ? band : 0, r1 = nb[South] >= 0 ? lx - band : lx;
-  const int64_t c0 = nb[West] >= 0 ? round_up(band, 4) : 0;
-  const int64_t c1 = nb[East] >= 0 ? round_down(ly - band, 4) : ly;
+  const InteriorSplit sp = interior_split(blk_.lx, blk_.ly, blk_.nbr, std::max(band, k));
   if (part == 0) {
-    Box in{r0, r1, c0, c1};
-    gpu::tb_step(src, dst, g, &in, 1, k, r, st, waves_target, -1, rl);
+    gpu::tb_step(src, dst, g, &sp.interior, 1, k, r, st, waves_target, -1, rl);
   } else {
-    Box b[4] = {{0, r0, 0, ly}, {r1, lx, 0, ly}, {r0, r1, 0, c0}, {r0, r1, c1, ly}};
-    gpu::tb_step(src, dst, g, b, 4, k, r, st, waves_target, -1, rl);
+    gpu::tb_step(src, dst, g, sp.bands, 4, k, r, st, waves_target, -1, rl);
     // cur_ flips once per pass, after the boundary part.
   }
 }
@@ -862,16 +851,12 @@ int Solver::resident_span(const std::vector<PassPlan>& plan, size_t i) const {
   if (tr_->world() > 1 && !resident_force_ && device_users(P_.device >= 0 ? P_.device : 0) > 1)
     return 0;
   const int k = plan[i].k;
-  const bool ns = ns_active(), ew = ew_active();
   // Ghost validity after the first pass's (possible) exchange, then the
-  // bookkeeping of ensure_ghosts pass by pass: the span ends before a pass
-  // that would need an exchange.
-  int64_t gr = gr_, gc = gc_;
-  if ((ns && gr < k) || (ew && gc < k)) gr = gc = H_;
-  const Box box{open_side(North) ? -(ns ? gr - k : 0) : 0,
-                blk_.lx + (open_side(South) ? (ns ? gr - k : 0) : 0),
-                open_side(West) ? -(ew ? round_down(gc - k, 4) : 0) : 0,
-                blk_.ly + (open_side(East) ? (ew ? round_down(gc - k, 4) : 0) : 0)};
+  // bookkeeping of ensure_ghosts pass by pass on a copy: the span ends before
+  // a pass that would need an exchange.
+  GhostState gh = gh_;
+  if (gh.needs_exchange(sides_, k)) gh.refill(H_);
+  Box box;  // the first pass's
   int n = 0, nchk = 0;
   for (size_t j = i; j < plan.size(); ++j) {
     if (plan[j].k != k) break;
@@ -880,10 +865,10 @@ int Solver::resident_span(const std::vector<PassPlan>& plan, size_t i) const {
     if (plan[j].rl != 0 &&
         (!gated() || plan[j].rl % 2 != 0 || nchk == gpu::kTbResidentMaxChecks))
       break;
-    if (n > 0 && ((ns && gr < k) || (ew && gc < k))) break;
+    if (n > 0 && gh.needs_exchange(sides_, k)) break;
     if (res_span_max_ > 0 && n == res_span_max_) break;
-    if (ns) gr -= k;
-    if (ew) gc = round_down(gc - k, 4);
+    const auto ext = gh.advance(sides_, k, true);
+    if (n == 0) box = grown_box(blk_.lx, blk_.ly, sides_, ext.first, ext.second);
     ++n;
     if (plan[j].rl != 0) ++nchk;
   }
@@ -901,8 +886,7 @@ void Solver::enqueue_resident(const std::vector<PassPlan>& plan, size_t i0, int 
   // ghost columns and rows the bookkeeping already treats as stale.
   const int64_t ex0 = stat_exchanges_;
   const auto ext = ensure_ghosts(k, s_comp_);
-  const Box box{open_side(North) ? -ext.first : 0, blk_.lx + (open_side(South) ? ext.first : 0),
-                open_side(West) ? -ext.second : 0, blk_.ly + (open_side(East) ? ext.second : 0)};
+  const Box box = grown_box(blk_.lx, blk_.ly, sides_, ext.first, ext.second);
   for (int j = 1; j < n; ++j) (void)ensure_ghosts(k, s_comp_);
   HEAT_CHECK(stat_exchanges_ - ex0 <= 1, "resident span of %d passes needs an exchange", n);
   const int cur0 = cur_;
@@ -949,8 +933,8 @@ void Solver::enqueue_resident(const std::vector<PassPlan>& plan, size_t i0, int 
     rec.rl = plan[i0 + size_t(j)].rl;
     rec.cur0 = cur0;
     rec.cur1 = j + 1 == n ? out : -1;  // only the last pass's state is in memory
-    rec.gr1 = gr_;
-    rec.gc1 = gc_;
+    rec.gr1 = gh_.gr;
+    rec.gc1 = gh_.gc;
     rec.span = j + 1;
     rec.er = ext.first;
     rec.ec = ext.second;
@@ -965,21 +949,11 @@ void Solver::enqueue_resident(const std::vector<PassPlan>& plan, size_t i0, int 
 void Solver::compute_cpu(int k, int rl, int64_t er, int64_t ec) {
   TraceRange trace("heat.compute");
   PhaseScope phase(this, kCompute, nullptr);
-  const gpu::StencilGeom sg = geom();  // the plate extended beyond insulated sides
-  cpu::Geom g;
-  g.pitch = sg.pitch;
-  g.gx0 = sg.gx0;
-  g.gy0 = sg.gy0;
-  g.nx = sg.nx;
-  g.ny = sg.ny;
-  g.cx = sg.cx;
-  g.cy = sg.cy;
-  g.numerics = sg.numerics;
+  const cpu::Geom g = cpu::geom_of(geom());  // the plate extended beyond insulated sides
   for (int j = 0; j < k; ++j) {
-    const int64_t e = k - 1 - j;
-    Box b{open_side(North) ? -(er + e) : 0, blk_.lx + (open_side(South) ? er + e : 0),
-          open_side(West) ? -(ec + e) : 0, blk_.ly + (open_side(East) ? ec + e : 0)};
-    const bool at = j == rl - 1;
+    const SubPass sp = sub_pass(k, rl, 1, j);
+    const Box b = grown_box(blk_.lx, blk_.ly, sides_, er + sp.grow, ec + sp.grow);
+    const bool at = sp.takes_resid;
     const float r = P_.source ? cpu::step_source(field_[cur_], field_[cur_ ^ 1], q_, g, b, at)
                               : cpu::step(field_[cur_], field_[cur_ ^ 1], g, b, at);
     if (at) cpu_resid_ = r;
@@ -988,36 +962,17 @@ void Solver::compute_cpu(int k, int rl, int64_t er, int64_t ec) {
 }
 
 std::pair<int64_t, int64_t> Solver::ensure_ghosts(int k, hipStream_t st) {
-  // gr_/gc_: how many ghost rows/columns of field_[cur_] hold the current
-  // time level.  A k-step pass needs k; an exchange refills H.  Invariant:
-  // they never exceed the depth of the last exchange of this buffer -- N/S
-  // row messages carry the sender's own (stale) ghost columns into our
-  // corners, and only the corner unpack of THAT exchange overwrites them up
-  // to its depth (the overlap schedule exchanges k < H and then claims 0;
-  // tests/test_gpu_loopback.py::test_loopback_deep_halo_chunked mixes depths
-  // and short tail segments on 2 x 2 ranks).  The pass
-  // then also updates the (valid - k) ghost rows/columns next to the block,
-  // which become the valid ghosts of the next level.  Only axes that are
-  // decomposed or have an insulated side count (global quantities), so every
-  // rank makes the same decision.
-  const bool ns = ns_active(), ew = ew_active();
-  if ((ns && gr_ < k) || (ew && gc_ < k)) {
+  // The bookkeeping and its invariant: GhostState (plan.hpp).
+  if (gh_.needs_exchange(sides_, k)) {
     exchange(cur_, H_, st);
-    gr_ = gc_ = H_;
+    gh_.refill(H_);
   }
-  HEAT_CHECK(gr_ <= H_ && gc_ <= H_, "ghost depth %lld/%lld beyond the exchanged %d",
-             (long long)gr_, (long long)gc_, H_);
-  // TB boxes start on a float4 column: round the column extension down.
-  const bool tb = tb_kernel();
-  const int64_t er = ns ? gr_ - k : 0;
-  const int64_t ec = ew ? (tb ? round_down(gc_ - k, 4) : gc_ - k) : 0;
-  gr_ = er;
-  gc_ = ec;
-  return {er, ec};
+  HEAT_CHECK(gh_.gr <= H_ && gh_.gc <= H_, "ghost depth %lld/%lld beyond the exchanged %d",
+             (long long)gh_.gr, (long long)gh_.gc, H_);
+  return gh_.advance(sides_, k, tb_kernel());
 }
 
 void Solver::enqueue_pass(int k, int rl) {
-  const auto& nb = blk_.nbr;
   const bool resid = rl > 0;
   // With world > 1 every rank of the grid has a neighbour.
   const bool multi = tr_->world() > 1;
@@ -1033,12 +988,8 @@ void Solver::enqueue_pass(int k, int rl) {
     // Gated runs zero the residual word in the judge kernel instead.
     if (resid && !gated()) HIP_CHECK(hipMemsetAsync(d_resid_, 0, 4, s_comp_));
     const bool tb = tb_kernel();
-    const int64_t lx = blk_.lx, ly = blk_.ly;
     const int band = sched_ == Schedule::Pipeline ? H_ : k;
-    const int64_t ir0 = nb[North] >= 0 ? band : 0, ir1 = nb[South] >= 0 ? lx - band : lx;
-    const int64_t ic0 = nb[West] >= 0 ? round_up(band, 4) : 0;
-    const int64_t ic1 = nb[East] >= 0 ? round_down(ly - band, 4) : ly;
-    const bool interior_ok = ir1 > ir0 && ic1 > ic0;
+    const bool interior_ok = !interior_split(blk_.lx, blk_.ly, blk_.nbr, band).interior.empty();
     // Which work goes on the side stream of the overlap schedules.  Eagerly
     // the exchange does (the high-priority comm stream, so RCCL's kernels
     // are dispatched ahead of queued stencil workgroups).  Under capture a
@@ -1056,7 +1007,7 @@ void Solver::enqueue_pass(int k, int rl) {
       // previous pass (or now, if stale).  Compute the H-deep boundary bands,
       // then post the NEXT pass's exchange (its send rows/columns all lie in
       // the bands) concurrent with the interior launch.
-      if (gr_ < H_ || gc_ < H_) {
+      if (gh_.gr < H_ || gh_.gc < H_) {
         if (comm_on_side) {
           HIP_CHECK(hipEventRecord(ev_ready_, s_comp_));
           HIP_CHECK(hipStreamWaitEvent(s_comm_, ev_ready_, 0));
@@ -1088,7 +1039,7 @@ void Solver::enqueue_pass(int k, int rl) {
       }
       HIP_CHECK(hipEventRecord(ev_halo_, s_comm_));
       comm_pending_ = true;
-      gr_ = gc_ = H_;  // for the buffer that becomes cur_ below
+      gh_.refill(H_);  // for the buffer that becomes cur_ below
     } else if (sched_ == Schedule::Overlap && tb && interior_ok) {
       // Exchange-first: exchange || interior, then the boundary bands.
       HIP_CHECK(hipEventRecord(ev_ready_, s_comp_));
@@ -1104,11 +1055,11 @@ void Solver::enqueue_pass(int k, int rl) {
       }
       HIP_CHECK(hipStreamWaitEvent(s_comp_, ev_halo_, 0));
       compute_gpu(k, rl, true, 1);
-      gr_ = gc_ = 0;
+      gh_ = {};
     } else if (sched_ == Schedule::Overlap) {
       exchange(cur_, k, s_comp_);
       compute_gpu(k, rl, false, 0);
-      gr_ = gc_ = 0;
+      gh_ = {};
     } else {
       // Sync (default): one launch per pass, one exchange per H/k passes.
       const auto ext = ensure_ghosts(k, s_comp_);
@@ -1133,13 +1084,12 @@ void Solver::enqueue_pass(int k, int rl) {
       }
     }
   } else {
-    std::pair<int64_t, int64_t> ext{0, 0};
-    if (ghosts) ext = ensure_ghosts(k, nullptr);
+    const auto ext = ghosts ? ensure_ghosts(k, nullptr) : std::pair<int64_t, int64_t>{0, 0};
     compute_cpu(k, rl, ext.first, ext.second);
   }
   rec.cur1 = cur_;
-  rec.gr1 = gr_;
-  rec.gc1 = gc_;
+  rec.gr1 = gh_.gr;
+  rec.gc1 = gh_.gc;
   pass_log_.push_back(rec);
   step_ += k;
   ++stat_passes_;
@@ -1182,8 +1132,8 @@ bool Solver::enqueue_chain(const std::vector<PassPlan>& plan, size_t i0, int n) 
     rec.rl = 0;
     rec.cur0 = (cur0 + j) & 1;
     rec.cur1 = (cur0 + j + 1) & 1;
-    rec.gr1 = gr_;
-    rec.gc1 = gc_;
+    rec.gr1 = gh_.gr;
+    rec.gc1 = gh_.gc;
     pass_log_.push_back(rec);
   }
   cur_ = out;
@@ -1331,7 +1281,7 @@ void Solver::launch_segment(const std::vector<PassPlan>& plan, int64_t n, int64_
     *checks = std::move(e.checks);
     return;
   }
-  const auto key = std::make_tuple(n, phase, cur_, gr_, gc_);
+  const auto key = std::make_tuple(n, phase, cur_, gh_.gr, gh_.gc);
   auto it = graphs_.find(key);
   if (it == graphs_.end()) {
     const int64_t p_before = stat_passes_, e_before = stat_exchanges_, r_before = stat_resident_,
@@ -1360,8 +1310,8 @@ void Solver::launch_segment(const std::vector<PassPlan>& plan, int64_t n, int64_
     if (tr_->world() > 1 && std::strcmp(tr_->name(), "rccl") == 0) rccl_graphs_ = true;
     HIP_CHECK(hipGraphDestroy(graph));
     e.cur_after = cur_;
-    e.gr_after = gr_;
-    e.gc_after = gc_;
+    e.gr_after = gh_.gr;
+    e.gc_after = gh_.gc;
     e.passes = stat_passes_ - p_before;
     e.exchanges = stat_exchanges_ - e_before;
     e.resident = resident_used_;
@@ -1378,8 +1328,8 @@ void Solver::launch_segment(const std::vector<PassPlan>& plan, int64_t n, int64_
   HIP_CHECK(hipGraphLaunch(it->second.exec, s_comp_));
   resident_used_ = resident_used_ || it->second.resident;
   cur_ = it->second.cur_after;
-  gr_ = it->second.gr_after;
-  gc_ = it->second.gc_after;
+  gh_.gr = it->second.gr_after;
+  gh_.gc = it->second.gc_after;
   step_ = step_before + n;
   stat_passes_ += it->second.passes;
   stat_exchanges_ += it->second.exchanges;
@@ -1505,8 +1455,8 @@ void Solver::run_gated(int64_t steps, RunStats& s) {
   // the error see the check's state, as on the host-judged path.
   if (p->rl == p->k && p->cur1 >= 0) {
     cur_ = p->cur1;
-    gr_ = p->gr1;
-    gc_ = p->gc1;
+    gh_.gr = p->gr1;
+    gh_.gc = p->gc1;
   } else {
     replay_check(*p);
   }
@@ -1542,12 +1492,12 @@ void Solver::replay_check(const PassRec& p) {
   // most rl <= k valid ghost levels, which the pass itself had.
   const int64_t er0 = p.span > 1 ? p.er : 0, ec0 = p.span > 1 ? p.ec : 0;
   for (int left = p.rl; left > 0;) {
-    const int d = gpu::tb_depth_supported(left) ? left : (left % 8 != 0 ? left % 8 : 8);
+    const int d = replay_depth(left, gpu::tb_depth_supported(left));
     left -= d;
     compute_gpu(d, 0, false, 0, 0, std::max<int64_t>(er0, left), std::max<int64_t>(ec0, left));
     cur_ ^= 1;
   }
-  gr_ = gc_ = 0;  // the replayed buffer's ghosts are stale
+  gh_ = {};  // the replayed buffer's ghosts are stale
   sync_watch();
 }
 
@@ -1843,7 +1793,7 @@ void Solver::load_owned(const float* host, int64_t host_pitch, int64_t step) {
   }
   synchronize();
   step_ = step;
-  gr_ = gc_ = 0;
+  gh_ = {};
 }
 
 void Solver::refine(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy, int order,
@@ -1893,7 +1843,7 @@ void Solver::refine(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t 
     for (int b = 0; b < 2; ++b) refine_block(field_[b], L_.pitch, lx, ly, S, CC, rows, cols);
   }
   step_ = step;
-  gr_ = gc_ = 0;
+  gh_ = {};
 }
 
 void Solver::set_source(const float* S, int64_t CR, int64_t CC, int64_t fx, int64_t fy,

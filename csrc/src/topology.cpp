@@ -133,14 +133,26 @@ Layout Layout::make(int64_t lx, int64_t ly, int halo) {
 
 Box span_box(const Cart& cart, const Block& b, int depth, int m, unsigned insulated,
              unsigned periodic) {
+  const Sides s = make_sides(cart, b, insulated, periodic);
+  GhostState g;
+  g.refill(int64_t(m) * depth);
+  const auto e = g.advance(s, depth, true);
+  return grown_box(b.lx, b.ly, s, e.first, e.second);
+}
+
+Sides make_sides(const Cart& cart, const Block& b, unsigned insulated, unsigned periodic) {
   // A periodic axis is decomposed and both its sides are open, as if insulated.
   insulated |= periodic_sides(periodic);
-  const bool ns = cart.px > 1 || (insulated & 3) != 0, ew = cart.py > 1 || (insulated & 12) != 0;
   auto open = [&](int d) { return b.nbr[size_t(d)] >= 0 || ((insulated >> d) & 1) != 0; };
-  const int64_t gr = ns ? int64_t(m - 1) * depth : 0;
-  const int64_t gc = ew ? round_down(int64_t(m - 1) * depth, 4) : 0;
-  return Box{open(North) ? -gr : 0, b.lx + (open(South) ? gr : 0),
-             open(West) ? -gc : 0, b.ly + (open(East) ? gc : 0)};
+  return {{open(North), open(South), open(West), open(East)},
+          cart.px > 1 || (insulated & 3) != 0, cart.py > 1 || (insulated & 12) != 0};
+}
+
+InteriorSplit interior_split(int64_t lx, int64_t ly, const std::array<int, 4>& nbr, int64_t band) {
+  const int64_t r0 = nbr[North] >= 0 ? band : 0, r1 = nbr[South] >= 0 ? lx - band : lx;
+  const int64_t c0 = nbr[West] >= 0 ? round_up(band, 4) : 0;
+  const int64_t c1 = nbr[East] >= 0 ? round_down(ly - band, 4) : ly;
+  return {{r0, r1, c0, c1}, {{0, r0, 0, ly}, {r1, lx, 0, ly}, {r0, r1, 0, c0}, {r0, r1, c1, ly}}};
 }
 
 int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned insulated,
