@@ -224,3 +224,34 @@ def run_tune(world, cfg_kwargs, tmp_path, transport="auto"):
              join=True)
     with open(out) as f:
         return json.load(f)
+
+
+def lifecycle_worker(rank, world, port, cfg_kwargs, plan):
+    """A gloo rank on the CPU backend plays a lifecycle scenario
+    (lifecycle_cases.play: run, read, replace the state, continue; every check
+    is an assertion of its own).  A failing rank ends the spawn, so its peers
+    never wait for it."""
+    import torch.distributed as dist
+
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank),
+                      WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    from parallel_heat_amd import HeatConfig, HeatSolver
+    from parallel_heat_amd.parallel.comm import DistInfo
+
+    from . import lifecycle_cases
+
+    s = HeatSolver(HeatConfig(**cfg_kwargs), transport="torch",
+                   dist_info=DistInfo(rank, world, rank))
+    lifecycle_cases.play(s, plan)
+    s.close()
+    dist.barrier()
+    dist.destroy_process_group()
+
+
+def run_lifecycle(world, cfg_kwargs, plan):
+    """lifecycle_cases.play of `plan` on every rank of a world of processes."""
+    import torch.multiprocessing as mp
+
+    mp.spawn(lifecycle_worker, args=(world, free_port(), cfg_kwargs, plan), nprocs=world,
+             join=True)
