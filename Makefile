@@ -103,7 +103,7 @@ clean:
 
 # Host-only self-test of the CPU components, plain and under ASan/UBSan.
 SELFTEST_SRCS := csrc/tests/selftest.cpp csrc/src/common.cpp csrc/src/topology.cpp \
-                 csrc/src/io.cpp csrc/src/cpu_backend.cpp
+                 csrc/src/tb_plan.cpp csrc/src/io.cpp csrc/src/cpu_backend.cpp
 $(BUILD)/selftest: $(SELFTEST_SRCS) $(HDRS)
 	@mkdir -p $(BUILD)
 	g++ -std=c++17 -O2 -g -Wall -Icsrc/include -mfma -mavx2 -fopenmp $(SELFTEST_SRCS) -o $@
@@ -137,7 +137,7 @@ refine-selftest-asan: $(BUILD)/refine-selftest-asan
 # The same for the heat source (the host twin of the source step and the
 # extended-table builder of its ghost cells).
 SOURCE_SELFTEST_SRCS := csrc/tests/source_selftest.cpp csrc/src/common.cpp csrc/src/topology.cpp \
-                        csrc/src/io.cpp csrc/src/cpu_backend.cpp
+                        csrc/src/tb_plan.cpp csrc/src/io.cpp csrc/src/cpu_backend.cpp
 $(BUILD)/source-selftest: $(SOURCE_SELFTEST_SRCS) $(HDRS)
 	@mkdir -p $(BUILD)
 	g++ -std=c++17 -O2 -g -Wall -Icsrc/include -mfma -mavx2 -fopenmp $(SOURCE_SELFTEST_SRCS) -o $@

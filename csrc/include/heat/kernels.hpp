@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "heat/io.hpp"
+#include "heat/tb_plan.hpp"
 #include "heat/topology.hpp"
 
 namespace heat::gpu {
@@ -40,62 +41,6 @@ struct StencilGeom {
   // non-zero writes nothing (see judge_check).
   const unsigned* gate = nullptr;
 };
-
-// Variant flags of the temporally blocked kernel (tb_step's `variant`; the
-// same names in parallel_heat_amd.ops.TbVariant).  Bits 0-1 choose the
-// register pipeline, the rest the build and the launch layout.
-namespace tbv {
-enum : int {
-  kRing3 = 0,           // 3-row rings, skew 1 (LAG 1)
-  kRing4 = 1,           // 4-row rings, skew 2 (LAG 2)
-  kRing2 = 2,           // 2-row rings + copy (LAG 0)
-  kRamp = 3,            // 3-row rings + compile-time ramp skip (LAG 3)
-  kPipeMask = 3,
-  kScalar = 4,          // scalar row update build (tbs; depth 12 lives here)
-  kPrefetch6 = 8,       // with kRamp: 6-row prefetch (retired, LAG 4)
-  kXcdGroups = 16,      // contiguous wave ranges per XCD
-  kAltDirection = 32,   // odd chunks stream bottom-up
-  kFloat2 = 64,         // float2 lanes, 128-column strips (tbn)
-  kForceAgePairs = 256, // age groups even at equal weights (tests)
-  kDiagNoStore = 1024,  // diagnostics: no output stores (wrong results)
-  kSplit = 2048,        // two-wave level-split pipelines (tbx; depths 8, 12)
-  kDiagCachedRows = 4096,  // diagnostics: cache-resident input rows (wrong results)
-  kNoAgePairs = 16384,  // never age-group (A/B of the weights)
-  kLinear = 32768,      // force the balanced linear plan (equal strip-rows per unit)
-  kNoLinear = 65536,    // never switch to it (by default it replaces a classic
-                        // plan that fills < 90 % of the launch's units)
-  kTile = 131072,       // workgroup tiles: 8 waves x R rows of a strip in VGPRs,
-                        // neighbour rows through LDS each step (tbw, tb_tile.hip)
-  kTileDpp = 262144,    // with kTile: DPP lane shifts instead of ds_bpermute
-  kShiftMixed = 524288, // with kSplit: west shift DPP, east ds_bpermute (tbxm, tb_split_mixed.hip)
-  // Defaults: depth <= 8 and small launches at 12; large launches at 12.
-  kDefault = kRamp | kScalar | kXcdGroups,  // 23
-  kDefaultDeep = kDefault | kSplit,         // 2071
-};
-}  // namespace tbv
-
-// Depths the temporally blocked kernel is instantiated for.
-constexpr int kTbMaxDepth = 8;    // 1..8: every build
-// Rows of the older : younger wave of a chunk pair at two waves per SIMD
-// (kTbAgePairs; HEAT_TB_AGE_RATIO sets it, <= 1 = off).  Off by default: it
-// evens the two waves' finish times (busy fraction 0.77 -> 0.81) but not the
-// launch span, which the SIMD's combined issue rate sets
-// (profiles/tb_wave_timeline_r1.md).
-constexpr double kTbAgeRatio = 1.0;
-// Level-split pipelines at two per SIMD: the first-dispatched half of the
-// grid takes 1.7x the rows of the second half in each pair of adjacent
-// chunks: +4-7 % at 2048..8192-row blocks (profiles/tb_split_age_pairs_r2.md).
-constexpr double kTbSplitAgeWeights[2] = {1.7, 1.0};
-// Linear plans of split pipelines at four blocks per CU: one share per
-// dispatch round (oldest first).
-constexpr double kTbLinearAgeWeights[4] = {2.0, 1.95, 1.15, 1.0};
-constexpr int kTbDeepDepth = 12;  // + 12: scalar ring-3+ramp build (variant bits 4|3)
-bool tb_depth_supported(int k);
-// Output columns per 256-column strip at depth k.
-// Output columns per TB strip (64 lanes x lane_cols, minus the overlap) and
-// the lane width of a variant (4: float4 lanes; variant bit 64: float2).
-int tb_strip_width(int k, int lane_cols = 4);
-int tb_lane_cols(int variant);
 
 // Fill every allocated cell (owned, ghost ring and padding) of a field with
 // the initial condition at its global coordinates (0 outside the plate).
@@ -198,37 +143,7 @@ int tb_auto_variant(int depth, int64_t strip_rows_per_simd);
 // ({start, end} s_memrealtime ticks (100 MHz), block, strip<<32 | chunk);
 // waves = buffer capacity in waves.  nullptr switches it off.
 void tb_set_stamps(unsigned long long* buf, int64_t waves);
-int tb_variant_lag(int variant);
-// The variant's build has the kTbDeepDepth instantiation (scalar ring-3+ramp).
-bool tb_variant_deep(int variant);
-// Bit 2048: each (strip, chunk) runs on a two-wave level-split pipeline
-// (depths 8 and 12; scalar ring-3+ramp variants only).
-bool tb_variant_split(int variant);
-// Launch-planner knobs of the TB kernel.  Defaults are the tuned values;
-// each HEAT_TB_* environment variable overrides its field when the process
-// first plans a launch (diagnostics and A/B sweeps), and tb_set_tuning()
-// replaces the whole set at run time (tests, tools).
-struct TbTuning {
-  int variant = -1;        // HEAT_TB_VARIANT: force a variant (-1: per launch)
-  int rounds = 0;          // HEAT_TB_ROUNDS: whole resident rounds per launch (0: from the work)
-  int min_len = 0;         // HEAT_TB_MINLEN: minimum chunk rows (0: max(depth, 8))
-  int waves = 0;           // HEAT_TB_WAVES: waves per launch of the solver (0: planner)
-  double edge_frac = 1.0;  // HEAT_TB_EDGE_FRAC: top/bottom edge chunk length factor
-  // HEAT_TB_AGE_WEIGHTS "w0,w1,.." (or HEAT_TB_AGE_RATIO r = {r, 1}): row
-  // shares of the age groups; empty = the built-in weights.
-  std::vector<double> age_weights;
-  int tile_rows = 0;       // HEAT_TB_TILE_ROWS: rows per wave of kTile launches (0: planner)
-  int tile_waves = 0;      // HEAT_TB_TILE_WAVES: waves per kTile workgroup, 8 or 16 (0: planner)
-  int tile_xl = -1;        // HEAT_TB_TILE_XL: kTile lane shifts, 0 DPP, 1 ds_bpermute,
-                           // 2 mixed (-1: mixed unless the variant has kTileDpp)
-  int tile_max_srps = 64;  // HEAT_TB_TILE_MAX: workgroup tiles below this many strip-rows
-                           // per SIMD (the automatic variant and Solver::tile_sized)
-  int nt = -1;             // HEAT_TB_NT: level-split rows non-temporal (1) or plain (0);
-                           // -1: non-temporal when a pass sweeps > kTbStreamBytes
-  int res_diag = 0;        // HEAT_TB_RES_DIAG: resident-tile timing diagnostics (bits 0-2
-                           // give WRONG results): bit 0 no neighbour wait, 1 no ghost reload,
-                           // 2 no publish; bit 3 every tile on the masked (edge) path
-};
+// The variant flags, TbTuning and the launch planners: heat/tb_plan.hpp.
 TbTuning tb_tuning();  // a copy of the current set
 void tb_set_tuning(const TbTuning& t);
 // Whole rounds of resident waves per launch (TbTuning::rounds; 0 = unset: the
@@ -238,9 +153,6 @@ int tb_default_rounds();
 int tb_resident_waves(int depth, int variant);
 // SIMDs of the current device (CUs x 4).
 int tb_simd_count();
-// Waves per SIMD the planner uses for a launch with this much work per SIMD
-// (strip-rows / SIMDs), at most max_per_simd.
-int tb_auto_waves_per_simd(int depth, int64_t strip_rows_per_simd, int max_per_simd);
 
 // Copy a box of a strided field to/from a contiguous buffer (E/W halos).
 void pack_box(const float* origin, int64_t pitch, const Box& box, float* buf, hipStream_t st);

@@ -131,10 +131,10 @@ int64_t halo_extent_limit(const Cart& cart, int64_t nx, int64_t ny, unsigned ins
                           unsigned periodic = 0);
 
 // Host-side resident plan of a box at `depth` on an MI355X (`cus` CUs): the
-// tile planner's shapes and choice (tb_resident.hip plan_res: the lowest
+// tile planner's shapes and choice (tb_plan.hpp resident_tile_plan: the lowest
 // tile_step_estimate among the shapes whose tiles are all co-resident) with
 // the co-resident workgroups per CU the occupancy API reports for gfx950
-// (also RES_SHAPES of parallel/model.py).  `heat --plan` uses it without a
+// (kResidentOccGfx950; also RES_SHAPES of parallel/model.py).  `heat --plan` uses it without a
 // GPU; the solver asks the device (gpu::tb_resident_shape).
 int resident_shape_static(const Box& box, int depth, int cus = 256);
 

@@ -19,7 +19,7 @@
 //    results are bitwise equal across kernels, depths and decompositions.
 #include <hip/hip_runtime.h>
 
-#include <cmath>
+#include <algorithm>
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
@@ -256,37 +256,6 @@ int grid_1d(int64_t n) { return int(std::min<int64_t>(ceil_div(n, 256), 256 * 16
 
 }  // namespace
 
-bool tb_depth_supported(int k) {
-  // 1..8 in every build; 12 in the scalar ring-3+ramp build only
-  // (tb_scalar.hip, HEAT_TB_DEEP).
-  return (k >= 1 && k <= kTbMaxDepth) || k == kTbDeepDepth;
-}
-
-int tb_strip_width(int k, int lane_cols) {
-  return 64 * lane_cols - 2 * int(round_up(k, lane_cols));
-}
-int tb_lane_cols(int variant) { return (variant & tbv::kFloat2) ? 2 : 4; }
-
-int tb_variant_lag(int variant) {
-  const int pipe = variant & tbv::kPipeMask;
-  if (pipe == tbv::kRamp && (variant & tbv::kPrefetch6)) return 4;  // retired
-  switch (pipe) {
-    case tbv::kRing4: return 2;
-    case tbv::kRing2: return 0;
-    case tbv::kRamp: return 3;
-    default: return 1;
-  }
-}
-
-bool tb_variant_split(int variant) {
-  // Level-split two-wave pipelines (tb_split.hip; scalar ring-3+ramp).
-  return (variant & tbv::kSplit) && tb_variant_deep(variant);
-}
-
-bool tb_variant_deep(int variant) {
-  return (variant & tbv::kScalar) && !(variant & tbv::kFloat2) && tb_variant_lag(variant) == 3;
-}
-
 namespace {
 TbTuning tuning_from_env() {
   TbTuning t;
@@ -337,7 +306,6 @@ void tb_set_tuning(const TbTuning& t) {
 
 int tb_default_rounds() { return tb_tuning().rounds; }
 
-namespace {
 bool tb_trace_enabled() {
   static const bool on = [] {
     const char* e = std::getenv("HEAT_TB_TRACE");
@@ -354,95 +322,54 @@ void tb_trace_once(const char* line) {
   seen.emplace_back(line);
   std::fputs(line, stderr);
 }
-}  // namespace
 
-int tb_simd_count() {
-  static std::map<int, int> cache;
+int tb_device_memo(TbMemo which, int a, int b, int c, int (*compute)(int, int, int)) {
+  static std::map<std::tuple<int, int, int, int, int>, int> cache;
   static std::mutex mu;
   int dev = 0;
   HIP_CHECK(hipGetDevice(&dev));
+  const auto key = std::make_tuple(int(which), dev, a, b, c);
+  {
+    std::lock_guard<std::mutex> lk(mu);
+    if (auto it = cache.find(key); it != cache.end()) return it->second;
+  }
+  const int v = compute(a, b, c);  // unlocked: it may ask the memo itself
   std::lock_guard<std::mutex> lk(mu);
-  auto it = cache.find(dev);
-  if (it != cache.end()) return it->second;
-  int cus = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  return cache.emplace(dev, std::max(1, cus) * 4).first->second;
+  return cache.emplace(key, v).first->second;
 }
 
-int tb_auto_waves_per_simd(int depth, int64_t strip_rows_per_simd, int max_per_simd) {
-  // Fewer, longer chunks for small problems: each chunk pays a ~2K-row
-  // pipeline ramp, and more waves per SIMD only buy latency hiding.  The
-  // thresholds come from the waves sweep over slab heights 512..8192
-  // (tools/sweep_waves.sh, profiles/tb_waves_per_simd_r1.md): at K=8 one
-  // wave per SIMD wins below ~48 strip-rows per SIMD, two below ~100.
-  int w = max_per_simd;
-  if (strip_rows_per_simd < 6 * int64_t(depth)) w = 1;
-  else if (strip_rows_per_simd * 2 < 25 * int64_t(depth)) w = 2;
-  return std::max(1, std::min(w, max_per_simd));
+int tb_simd_count() {
+  return tb_device_memo(TbMemo::kSimds, 0, 0, 0, [](int, int, int) {
+    int dev = 0, cus = 0;
+    HIP_CHECK(hipGetDevice(&dev));
+    HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    return std::max(1, cus) * 4;
+  });
 }
 
 int tb_resident_waves(int depth, int variant) {
   // Cached per (device, depth, variant): CUs x resident blocks per CU x 4 waves.
-  static std::map<std::tuple<int, int, int>, int> cache;
-  static std::mutex mu;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  auto key = std::make_tuple(dev, depth, variant);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  int cus = 0;
-  HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-  const int lag = tb_variant_lag(variant);
-  if (tb_variant_split(variant)) {
-    // Work units are two-wave pipelines, two per block.
-    const int occ = (variant & tbv::kShiftMixed)
-                        ? tb_exp("the mixed-shift split build (kShiftMixed)").tbxm_occupancy_split(depth)
-                        : tbx::occupancy_split(depth);
-    const int w = std::max(1, cus * std::max(1, occ) * 2);
-    cache.emplace(key, w);
-    return w;
-  }
-  const int per_cu = (variant & tbv::kFloat2)  ? tb_exp("the float2-lane build (kFloat2)").tbn_occupancy(depth, lag)
-                     : (variant & tbv::kScalar) ? tbs::occupancy(depth, lag)
-                                                : tb_exp("the packed build (no kScalar)").tbp_occupancy(depth, lag);
-  const int w = std::max(1, cus * std::max(1, per_cu) * 4);
-  cache.emplace(key, w);
-  return w;
+  return tb_device_memo(TbMemo::kStreamWaves, depth, variant, 0, [](int depth, int variant, int) {
+    const int cus = tb_simd_count() / 4;
+    const int lag = tb_variant_lag(variant);
+    if (tb_variant_split(variant)) {
+      // Work units are two-wave pipelines, two per block.
+      const int occ = (variant & tbv::kShiftMixed)
+                          ? tb_exp("the mixed-shift split build (kShiftMixed)").tbxm_occupancy_split(depth)
+                          : tbx::occupancy_split(depth);
+      return std::max(1, cus * std::max(1, occ) * 2);
+    }
+    const int per_cu = (variant & tbv::kFloat2)  ? tb_exp("the float2-lane build (kFloat2)").tbn_occupancy(depth, lag)
+                       : (variant & tbv::kScalar) ? tbs::occupancy(depth, lag)
+                                                  : tb_exp("the packed build (no kScalar)").tbp_occupancy(depth, lag);
+    return std::max(1, cus * std::max(1, per_cu) * 4);
+  });
 }
 
-int tb_default_variant(int depth) {
-  if (const int v = tb_tuning().variant; v >= 0) return v;
-  // Ring-3 + ramp skip, scalar build, XCD-grouped blocks (23); at depth 12
-  // on large launches as two-wave level-split pipelines with ds_bpermute
-  // lane shifts (2071): +5 % in bench.py, +9-10 % in the interleaved kernel
-  // A/B (profiles/tb_wave_timeline_r1.md).  tb_step picks per launch from
-  // the work size (tb_auto_variant).
-  return depth == kTbDeepDepth ? tbv::kDefaultDeep : tbv::kDefault;
-}
+int tb_default_variant(int depth) { return tb_default_variant(depth, tb_tuning()); }
 
 int tb_auto_variant(int depth, int64_t strip_rows_per_simd) {
-  if (const int v = tb_tuning().variant; v >= 0) return v;
-  // The split pipelines need about 64 strip-rows per SIMD to pay for their
-  // second wave: below that (the per-rank blocks of 4-8 GPU runs: 1024 x
-  // 8192, 2048 x 4096, 1536 x 8192, ...) one wave per (strip, chunk) at
-  // depth 12 is 8-12 % faster, above it the split is 2-4 % faster
-  // (profiles/tb_block_shapes_r2.md).
-  // Below 64 (the 8-GPU blocks 1024 x 8192 and 2048 x 4096 and their
-  // deep-halo passes, 1536-row blocks) the workgroup tiles win: +6-10 % over
-  // one wave per chunk inside the plate at 36, and +36-38 % on blocks with a
-  // plate edge (the first and last rank, whose time the max over ranks
-  // reports) at 36 and 54, where one wave per chunk loses 8 % inside the
-  // plate (profiles/r3_tile.md).  Even depths only (the tile runs steps in
-  // pairs).  From 64 the split pipelines keep the edge ranks within 2 %.
-  if (depth >= 4 && depth % 2 == 0 && strip_rows_per_simd < tb_tuning().tile_max_srps)
-    return tbv::kTile | tbv::kXcdGroups;
-  if (depth == kTbDeepDepth && strip_rows_per_simd < 64) return tbv::kDefault;
-  // Depth 8 on whole-GPU plates (the remainder passes of 1000 = 82 x 12 +
-  // 8 + 8 at 8192^2: 288 strip-rows per SIMD) as split pipelines too:
-  // bench 5.21-5.22 vs 5.19-5.21 interleaved (profiles/r5_stores.md).
-  if (depth == 8 && strip_rows_per_simd >= 256) return tbv::kDefaultDeep;
-  return tb_default_variant(depth);
+  return tb_auto_variant(depth, strip_rows_per_simd, tb_tuning());
 }
 
 void init_field(float* origin, const Layout& L, int64_t gx0, int64_t gy0, int64_t nx, int64_t ny,
@@ -524,11 +451,6 @@ bool split_pk_enabled() {
   return on;
 }
 
-// Field bytes one pass must sweep before the level-split launches stream
-// their rows (kTbStreamRows): 3/4 of the 256 MB MALL (4096 x 8192 = 134 MB
-// measured faster plain, 8192^2 = 268 MB non-temporal).
-constexpr int64_t kTbStreamBytes = int64_t(192) << 20;
-
 void tb_step(const float* src, float* dst, const StencilGeom& g, const Box* boxes, int nbox,
              int depth, unsigned* resid, hipStream_t st, int waves_target, int variant,
              int res_level, TbChain* chain) {
@@ -537,285 +459,51 @@ void tb_step(const float* src, float* dst, const StencilGeom& g, const Box* boxe
   HEAT_CHECK(res_level >= 0 && res_level <= depth, "residual level %d of a depth-%d pass",
              res_level, depth);
   if (res_level == depth || resid == nullptr) res_level = 0;  // 0: the last step
-  const bool forced = variant >= 0 || tb_tuning().variant >= 0;
   const TbTuning tune = tb_tuning();
-  if (variant < 0) {
-    // Both defaults use float4 lanes (same strip width).
-    const int W4 = tb_strip_width(depth, 4);
-    int64_t rows4 = 0;
-    for (int b = 0; b < nbox; ++b)
-      if (!boxes[b].empty()) rows4 += ceil_div(boxes[b].cols(), W4) * boxes[b].rows();
-    variant = tb_auto_variant(depth, rows4 / tb_simd_count());
-    // Even depths only the tile kernel builds (10, 14, 16: checks every 10k
-    // steps on tile-sized blocks) stay on it whatever the launch size: a
-    // deep-halo box grown past the tile threshold (Solver::tile_sized_at
-    // judges the owned block) is still a valid tile launch, only slower.
-    if (!tb_depth_supported(depth) && depth % 2 == 0 && depth <= 16)
-      variant = tbv::kTile | tbv::kXcdGroups;
-  }
+  const bool forced = variant >= 0 || tune.variant >= 0;
+  const int simds = tb_simd_count();
   // The tile kernel takes any even depth up to 16 (Solver picks 10 for
   // checks every 10k steps on tile-sized blocks); the streaming kernels the
-  // built ones.
-  const bool tile_depth = (variant & tbv::kTile) && depth % 2 == 0 && depth <= 16;
-  HEAT_CHECK(tb_depth_supported(depth) || tile_depth, "unsupported TB depth %d (variant %d)", depth,
-             variant);
+  // built ones.  A tile variant at an odd depth comes back as a streaming one.
+  variant = tb_choose_variant(variant, depth, boxes, nbox, simds, tune);
+  HEAT_CHECK(tb_depth_supported(depth) || ((variant & tbv::kTile) && depth <= 16),
+             "unsupported TB depth %d (variant %d)", depth, variant);
   if (variant & tbv::kTile) {
-    // The tile kernel runs steps in (down, up) pairs: even depths only; an
-    // odd pass (a remainder or a check-cut pass) streams, with the default
-    // single-wave build (scalar update + ramp; dropping only the tile bits
-    // left the packed build, an experiment kernel since round 6).
-    if (depth % 2 == 0) {
-      tbw::step(src, dst, g, boxes, nbox, depth, resid, res_level, st, variant, tune);
-      return;
-    }
-    variant = (variant & ~(tbv::kTile | tbv::kTileDpp | 3)) | tbv::kDefault;
+    tbw::step(src, dst, g, boxes, nbox, depth, resid, res_level, st, variant, tune);
+    return;
   }
   // Inner-level residuals: the level-split build at depth 12 (and the tiles).
-  HEAT_CHECK(res_level == 0 || (tb_variant_split(variant) && depth == kTbDeepDepth),
+  const bool split = tb_variant_split(variant);
+  HEAT_CHECK(res_level == 0 || (split && depth == kTbDeepDepth),
              "a residual at step %d of a depth-%d pass needs the depth-12 level-split or tile "
              "kernel (variant %d%s)", res_level, depth, variant, forced ? ", forced" : "");
   const int lag = tb_variant_lag(variant);
-  const int W = tb_strip_width(depth, tb_lane_cols(variant));
-  int64_t total_strip_rows = 0;
-  for (int b = 0; b < nbox; ++b)
-    if (!boxes[b].empty()) total_strip_rows += ceil_div(boxes[b].cols(), W) * boxes[b].rows();
-  // Age groups (kTbAgePairs) for launches of whole resident rounds: blocks
-  // dispatched earlier issue faster (the SIMD's arbitration favours older
-  // waves), so the grid is split into G parts (part a = the a-th share of
-  // the dispatch rounds) and older parts get more rows.  Default: two parts
-  // at kTbSplitAgeWeights for the level-split pipelines; none (kTbAgeRatio
-  // = 1) for single-wave pipelines.  HEAT_TB_AGE_WEIGHTS="w0,w1,..." (2-4
-  // parts) or HEAT_TB_AGE_RATIO=r (two parts r : 1) override; "1" = off.
-  // Four parts (one per round at 4 blocks per CU) measured slower than two
-  // whatever the weights (profiles/tb_split_age_pairs_r2.md).
-  const std::vector<double>& env_weights = tune.age_weights;
-  const bool split_v = tb_variant_split(variant);
-  int G = 0;  // age groups of this launch (0: none)
-  std::vector<double> weights;
-  auto set_weights = [&](int max_groups) {
-    if (!env_weights.empty())
-      weights = env_weights;
-    else if (split_v)
-      weights.assign(std::begin(kTbSplitAgeWeights), std::end(kTbSplitAgeWeights));
-    else
-      weights = {kTbAgeRatio, 1.0};
-    bool uneven = false;
-    for (double w : weights) uneven = uneven || w != weights[0] || w <= 0.0;
-    G = uneven && int(weights.size()) >= 2 && int(weights.size()) <= max_groups ? int(weights.size()) : 0;
-  };
-  if (variant & tbv::kForceAgePairs) {  // tests: even weights still group
-    set_weights(4);
-    if (G == 0) {
-      G = 2;
-      weights.assign(2, 1.0);
-    }
-  }
-  int bpc = 0;  // blocks per CU of the planned launch (0: set by the caller's waves_target)
-  if (waves_target <= 0) {
-    // Whole rounds of the resident wave capacity (a partial last round leaves
-    // SIMDs idle for the tail of the launch); by default with the number of
-    // waves per SIMD chosen from the work per SIMD.
-    const int resident = tb_resident_waves(depth, variant);
-    const int rounds = waves_target < 0 ? -waves_target : tune.rounds;
-    if (rounds > 0) {
-      waves_target = rounds * resident;
-    } else {
-      const int simds = tb_simd_count();
-      const int per_simd = tb_auto_waves_per_simd(depth, total_strip_rows / simds,
-                                                  std::max(1, resident / simds));
-      waves_target = simds * per_simd;
-      // Blocks per CU = dispatch rounds: single-wave pipelines put one wave
-      // per SIMD in a block, level-split blocks hold two pipelines (4 waves).
-      const int blocks_per_cu = split_v ? 2 * per_simd : per_simd;
-      bpc = blocks_per_cu;
-      if (G == 0 && blocks_per_cu >= 2 && !(variant & tbv::kFloat2) &&
-          !(variant & tbv::kNoAgePairs))
-        set_weights(blocks_per_cu);
-    }
-  }
-  const bool pairs = G > 0;
+  const int resident = waves_target <= 0 ? tb_resident_waves(depth, variant) : 0;
+  const TbPlan plan = tb_plan_launch(variant, depth, boxes, nbox, g.gx0, g.nx, g.pitch, waves_target,
+                                     resident, simds, tune);
+  if (plan.nbox == 0) return;
   TbArgs args{};
   args.src = src;
   args.dst = dst;
   args.resid = resid;
   args.res_level = res_level > 0 ? res_level : depth;
   args.g = g;
-  args.flags = ((variant & tbv::kXcdGroups) ? tbdetail::kTbXcdGroups : 0) |
-               ((variant & tbv::kAltDirection) ? tbdetail::kTbAltDirection : 0) |
-               ((variant & tbv::kDiagNoStore) ? tbdetail::kTbDiagNoStore : 0) |
-               ((variant & tbv::kDiagCachedRows) ? tbdetail::kTbDiagCachedRows : 0);
-  // Split rows into chunks so the whole launch has about waves_target waves,
-  // but never shorter than 4*depth rows (keeps the redundant 2*depth-row
-  // halo reads below ~50 %).
-  // Minimum chunk length in rows (multiples of depth; HEAT_TB_MINLEN overrides).
-  const int64_t min_len = tune.min_len > 0 ? tune.min_len : std::max<int64_t>(depth, 8);
-  int64_t len = std::max<int64_t>(min_len, ceil_div(total_strip_rows, waves_target));
-  // Rows whose chunk window reaches the global top/bottom row run the
-  // generic (masked) path: HEAT_TB_EDGE_FRAC < 1 gives them shorter chunks,
-  // as separate sub-boxes.  Default 1 (no edge sub-boxes) since the round-2
-  // main loop: the edge chunks at 0.75 finished ~30 us before the rest of an
-  // 8192^2 launch; bench.py 1.0 vs 0.95 / 0.9 / 0.75: +0.4 / +1.2 / +1.2 %
-  // (profiles/tb_edge_frac_r2.md).
-  const double edge_frac = tune.edge_frac;
-  int n = 0, waves = 0;
-  auto plan = [&](int64_t L) {
-    const int64_t edge_len = std::max<int64_t>(std::min<int64_t>(min_len, L),
-                                               int64_t(double(L) * edge_frac));
-    n = 0;
-    waves = 0;
-    auto add = [&](const Box& B, int64_t clen) {
-      if (B.empty()) return;
-      HEAT_CHECK(n < tbdetail::kMaxBoxes, "too many TB sub-boxes");
-      TbBox& t = args.box[n++];
-      t.r0 = B.r0;
-      t.r1 = B.r1;
-      t.c0 = B.c0;
-      t.c1 = B.c1;
-      t.nstrips = int(ceil_div(B.cols(), W));
-      t.chunk_len = int(std::min<int64_t>(clen, B.rows()));
-      t.nchunks = int(ceil_div(B.rows(), t.chunk_len));
-      if (pairs) {
-        // Units are groups of G chunks (G * chunk_len rows), one wave (or
-        // pipeline) of each age.
-        t.chunk_len = int(std::max<int64_t>(1, ceil_div(std::min<int64_t>(G * clen, B.rows()), G)));
-        t.nchunks = int(ceil_div(B.rows(), G * int64_t(t.chunk_len)));
-      }
-      t.wave_begin = waves;
-      waves += t.nstrips * t.nchunks * (pairs ? G : 1);
-    };
-    for (int b = 0; b < nbox; ++b) {
-      const Box& B = boxes[b];
-      if (B.empty()) continue;
-      HEAT_CHECK(B.c0 % 4 == 0, "TB box column start %lld not a multiple of 4", (long long)B.c0);
-      Box mid = B, top{}, bot{};
-      if (edge_len < L && B.rows() > 2 * L) {
-        // Local rows whose window [r - depth, r + depth] touches global row 0 / nx-1.
-        const int64_t top_end = 1 - g.gx0 + depth;          // first row clear of the top
-        const int64_t bot_begin = g.nx - 2 - g.gx0 - depth;  // last row clear of the bottom
-        if (B.r0 < top_end) {
-          const int64_t e = std::min(B.r1, std::max(top_end, B.r0 + edge_len));
-          top = Box{B.r0, e, B.c0, B.c1};
-          mid.r0 = e;
-        }
-        if (B.r1 - 1 > bot_begin && mid.r1 > mid.r0) {
-          const int64_t s0 = std::max(mid.r0, std::min(bot_begin + 1, B.r1 - edge_len));
-          bot = Box{s0, B.r1, B.c0, B.c1};
-          mid.r1 = s0;
-        }
-      }
-      // Units in plate order (top edge, middle, bottom edge): XCD groups
-      // take contiguous unit ranges, so the short edge units land on the
-      // first and the last XCD instead of all on the first (which then
-      // idled for the last ~15 % of the launch, tools/wave_timeline.py
-      // xcd_last_end_us).
-      add(top, edge_len);
-      add(mid, L);
-      add(bot, edge_len);
-    }
-  };
-  bool linear = variant & tbv::kLinear;
-  if (!linear) {
-    // Keep the total within waves_target (whole resident rounds): a few extra
-    // waves would form a nearly empty extra round.
-    plan(len);
-    for (int it = 0; it < 8 && waves > waves_target; ++it) {
-      len = std::max(len + 1, ceil_div(len * int64_t(waves), int64_t(waves_target)));
-      plan(len);
-    }
-    // Few long chunks per strip quantise badly: 565 strips x 131072 rows
-    // (131072^2 on one GPU, or a 16384-row slab of it) became 1130 two-wave
-    // pipelines for 2048 slots, 2.25 blocks per CU, every chunk touching the
-    // plate's top or bottom row (masked path).  Balanced linear plans ran
-    // those at 5.16 / 4.65 Tcells/s instead of 3.50 / 4.33; at 8192^2 (the
-    // classic plan fills 98 %) they lose 24 %: units that cross a strip end
-    // or split off the masked edge rows pay a second pipeline ramp, and in a
-    // one-round launch the slowest unit sets the time
-    // (profiles/r3_linear_plans.md).
-    linear = !(variant & tbv::kNoLinear) && waves < (9 * int64_t(waves_target)) / 10 &&
-             total_strip_rows >= 32 * int64_t(depth) * waves_target;
-  }
-  if (linear) {
-    // Balanced plan: the boxes as one strip-row sequence cut into equal
-    // ranges, one per unit (per group of G units with age pairs), so every
-    // unit -- and every SIMD -- gets the same rows whatever the shape.
-    n = 0;
-    int64_t total = 0;
-    for (int b = 0; b < nbox; ++b) {
-      const Box& B = boxes[b];
-      if (B.empty()) continue;
-      HEAT_CHECK(B.c0 % 4 == 0, "TB box column start %lld not a multiple of 4", (long long)B.c0);
-      TbBox& t = args.box[n++];
-      t.r0 = B.r0;
-      t.r1 = B.r1;
-      t.c0 = B.c0;
-      t.c1 = B.c1;
-      t.nstrips = int(ceil_div(B.cols(), W));
-      t.nchunks = 1;
-      t.chunk_len = int(std::min<int64_t>(B.rows(), INT32_MAX));
-      t.wave_begin = 0;
-      t.lin0 = total;
-      total += int64_t(t.nstrips) * B.rows();
-    }
-    if (n == 0) return;
-    // Long linear units accumulate the SIMD's age bias: with four blocks
-    // per CU every dispatch round gets its own row share
-    // (kTbLinearAgeWeights; 16384 x 131072 slab 4.70 -> 5.15 Tcells/s,
-    // profiles/r3_raw/r3age_a16384.log).
-    if (pairs && env_weights.empty() && split_v && bpc >= 4) {
-      weights.assign(std::begin(kTbLinearAgeWeights), std::end(kTbLinearAgeWeights));
-      G = int(weights.size());
-    }
-    const int Gl = pairs ? G : 1;
-    const int64_t units = std::max<int64_t>(
-        Gl, std::min<int64_t>(waves_target, total / std::max<int64_t>(1, min_len)));
-    waves = int(units / Gl * Gl);
-    args.lin_total = total;
-    args.lin_slack = 2 * int64_t(depth);
-    args.flags |= tbdetail::kTbLinear;
-  }
-  if (n == 0) return;
-  args.nbox = n;
-  args.total_waves = waves;
-  if (pairs) {
-    // wave_begin / total_waves count groups (units of one age).
-    for (int b = 0; b < n; ++b) args.box[b].wave_begin /= G;
-    args.total_waves = waves / G;
-    args.flags |= tbdetail::kTbAgePairs;
-    args.age_groups = G;
-    double tot = 0.0;
-    for (double w : weights) tot += w;
-    double acc = 0.0;
-    args.age_cum[0] = 0;
-    for (int a = 0; a < G; ++a) {
-      acc += weights[size_t(a)];
-      args.age_cum[a + 1] = a + 1 == G ? 1024 : int(std::lround(1024.0 * acc / tot));
-    }
-  }
-  const bool split = tb_variant_split(variant);
-  if (split && !(variant & tbv::kShiftMixed)) {
-    // Streaming rows when one pass sweeps more field than the MALL (256 MB)
-    // holds: its rows come back one sweep later, never from L2 or the MALL.
-    int64_t bytes = 0;
-    for (int b = 0; b < nbox; ++b)
-      if (!boxes[b].empty()) bytes += boxes[b].rows() * g.pitch * int64_t(sizeof(float));
-    const bool nt = tune.nt >= 0 ? tune.nt != 0 : bytes > kTbStreamBytes;
-    if (nt) args.flags |= tbdetail::kTbStreamRows;
-  }
+  args.nbox = plan.nbox;
+  args.total_waves = plan.total_waves;
+  args.flags = plan.flags;
+  args.age_groups = plan.age_groups;
+  std::copy(std::begin(plan.age_cum), std::end(plan.age_cum), args.age_cum);
+  args.lin_total = plan.lin_total;
+  args.lin_slack = plan.lin_slack;
+  std::copy(std::begin(plan.box), std::end(plan.box), args.box);
   if (tb_trace_enabled()) {
     // HEAT_TB_TRACE=1: each distinct plan once on stderr (planner checks).
     char line[320];
-    std::snprintf(line, sizeof line,
-                  "[heat tb] depth %d variant %d boxes %d strip_rows %lld waves_target %d bpc %d "
-                  "linear %d units %d age_groups %d cum %d,%d,%d,%d chunk0 %d nchunks0 %d nt %d\n",
-                  depth, variant, n, (long long)total_strip_rows, waves_target, bpc,
-                  int((args.flags & tbdetail::kTbLinear) != 0), waves, pairs ? G : 0,
-                  args.age_cum[1], args.age_cum[2], args.age_cum[3], args.age_cum[4],
-                  args.box[0].chunk_len, args.box[0].nchunks,
-                  int((args.flags & tbdetail::kTbStreamRows) != 0));
+    tb_plan_trace_line(line, depth, plan);
     tb_trace_once(line);
   }
   if (const Stamps sb = stamps_of_current_device(); sb.buf) {
-    const int64_t need = int64_t(waves) * (split ? 2 : 1);
+    const int64_t need = int64_t(plan.units) * (split ? 2 : 1);
     HEAT_CHECK(need <= sb.waves, "stamp buffer holds %lld waves, launch has %lld",
                (long long)sb.waves, (long long)need);
     args.stamps = sb.buf;
@@ -833,7 +521,7 @@ void tb_step(const float* src, float* dst, const StencilGeom& g, const Box* boxe
     HIP_CHECK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
     const bool fits = split && !(variant & tbv::kShiftMixed) && (args.flags & tbdetail::kTbStreamRows) &&
                       !(args.flags & tbdetail::kTbLinear) && !(args.flags & tbdetail::kTbAltDirection) &&
-                      n == 1 && resid == nullptr && depth == kTbDeepDepth && args.stamps == nullptr &&
+                      plan.nbox == 1 && resid == nullptr && depth == kTbDeepDepth && args.stamps == nullptr &&
                       int64_t(args.total_waves) * G <= chain->max_units && blocks <= cus * occ;
     if (tb_trace_enabled()) {
       char line[320];
@@ -843,7 +531,7 @@ void tb_step(const float* src, float* dst, const StencilGeom& g, const Box* boxe
                     chain->passes, int(split), int((variant & tbv::kShiftMixed) != 0),
                     int((args.flags & tbdetail::kTbStreamRows) != 0),
                     int((args.flags & tbdetail::kTbLinear) != 0),
-                    int((args.flags & tbdetail::kTbAltDirection) != 0), n, int(resid != nullptr), depth,
+                    int((args.flags & tbdetail::kTbAltDirection) != 0), plan.nbox, int(resid != nullptr), depth,
                     args.total_waves, G, chain->max_units, blocks, cus, occ, int(fits));
       tb_trace_once(line);
     }

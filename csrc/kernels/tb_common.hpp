@@ -3,6 +3,7 @@
 
 #include <hip/hip_runtime.h>
 
+#include <cstddef>
 #include <type_traits>
 
 #include "heat/init_fn.hpp"
@@ -10,13 +11,6 @@
 
 namespace heat::gpu::tbdetail {
 
-struct TbBox {
-  int64_t r0, r1, c0, c1;
-  int nstrips, nchunks, chunk_len, wave_begin;
-  int64_t lin0;  // linear plans: strip-rows of the boxes before this one
-};
-
-constexpr int kMaxBoxes = 16;
 // Rows of the LDS ring between the two stages of a level-split pipeline.
 constexpr int kSplitRing = 8;
 
@@ -48,6 +42,9 @@ struct TbArgs {
   int64_t lin_slack;
   TbBox box[kMaxBoxes];
 };
+// A kernel argument: the planners fill a TbPlan (heat/tb_plan.hpp), the
+// launchers copy it in; the layout is the kernels' and stays.
+static_assert(sizeof(TbArgs) == 1048 && offsetof(TbArgs, box) == 152 && sizeof(TbBox) == 56);
 
 // Convergence gate (StencilGeom::gate): once the judge kernel has set it,
 // every later stencil launch of the run returns at once (the queued passes
@@ -55,41 +52,6 @@ struct TbArgs {
 __device__ __forceinline__ bool gated(const unsigned* gate) {
   return gate != nullptr && *gate != 0u;  // uniform: one scalar load per wave
 }
-
-// Launch-time layout options (variant bits 16 and 32, see tb_step):
-//   kTbXcdGroups     remap blocks so each XCD (blocks b, b+8, ... under the
-//                    observed round-robin placement) gets a contiguous range
-//                    of waves: vertically adjacent chunks share one L2.
-//   kTbAltDirection  odd chunks stream bottom-up, so the 2K halo rows two
-//                    adjacent chunks both read are read at about the same
-//                    time (both at the start or both at the end).
-constexpr int kTbXcdGroups = 1;
-constexpr int kTbAltDirection = 2;
-//   kTbAgePairs      age groups: the G blocks a CU holds (dispatch rounds:
-//                    grid part a = round a) split each group of G adjacent
-//                    chunks unevenly, older (earlier-dispatched) blocks taking
-//                    more rows: the SIMD's issue arbitration favours older
-//                    waves, so with equal chunks the youngest set the launch
-//                    tail (tools/wave_timeline.py by_age_rank,
-//                    profiles/tb_split_age_pairs_r2.md).
-constexpr int kTbAgePairs = 4;
-//   kTbDiagNoStore   diagnostics: skip the output stores (wrong results; a
-//                    timing probe of the store traffic; variant bit 1024).
-constexpr int kTbDiagNoStore = 8;
-//   kTbDiagCachedRows diagnostics: every input row load reads one of the
-//                    chunk's first 4 rows (cache-resident; wrong results, a
-//                    probe of load latency; variant bit 4096).
-constexpr int kTbDiagCachedRows = 16;
-//   kTbLinear        balanced plan: unit u takes strip-rows [u, u+1) * total /
-//                    units of the box sequence (variant bit 32768), so every
-//                    SIMD gets the same work whatever the shape; a unit may
-//                    run several segments (strip / box / Dirichlet-mode ends).
-constexpr int kTbLinear = 32;
-//   kTbStreamRows    level-split launches take the streaming build
-//                    (tb_split_nt.hip: non-temporal row loads and stores)
-//                    when one pass sweeps more than the MALL holds
-//                    (kTbStreamBytes, HEAT_TB_NT overrides).
-constexpr int kTbStreamRows = 64;
 
 __device__ __forceinline__ bool in_interior(int64_t g, int64_t n) { return g >= 1 && g <= n - 2; }
 
@@ -121,6 +83,18 @@ __device__ __forceinline__ void group_max_atomic(unsigned m, unsigned* resid, un
 }
 
 }  // namespace heat::gpu::tbdetail
+
+namespace heat::gpu {
+// HEAT_TB_TRACE=1 (read once): each distinct launch plan line once on stderr
+// (stencil.hip; the streaming, tile and resident launchers).
+bool tb_trace_enabled();
+void tb_trace_once(const char* line);
+// Per-device memo of a query of the current device (its SIMDs, an
+// occupancy): compute(a, b, c) runs once per (which, device, a, b, c), not
+// under the memo's lock, so a query may use another memoised one.
+enum class TbMemo { kSimds, kStreamWaves, kTileOccupancy, kResidentOccupancy };
+int tb_device_memo(TbMemo which, int a, int b, int c, int (*compute)(int, int, int));
+}  // namespace heat::gpu
 
 namespace heat::gpu::tbp {
 bool launch(const tbdetail::TbArgs& args, int depth, int lag, hipStream_t st);

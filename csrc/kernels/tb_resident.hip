@@ -40,14 +40,7 @@
 // Results are bitwise those of separate passes (heat::stencil, the same
 // Tile code).  Reference: the per-rank compute of
 // mpi/mpi_heat_improved_persistent_stat.c:162-234, which this replaces.
-#include <algorithm>
-#include <cstdio>
 #include <cstdlib>
-#include <map>
-#include <mutex>
-#include <set>
-#include <string>
-#include <tuple>
 
 #include "heat/common.hpp"
 #include "heat/plan.hpp"
@@ -77,20 +70,8 @@ bool launch_res(const ResArgs& ra, int rows, int waves, int xl, int blocks, hipS
 }
 
 int cached_occupancy_res(int rows, int waves, int xl) {
-  static std::map<std::tuple<int, int, int, int>, int> cache;
-  static std::mutex mu;
-  int dev = 0;
-  HIP_CHECK(hipGetDevice(&dev));
-  std::lock_guard<std::mutex> lk(mu);
-  const auto key = std::make_tuple(dev, rows, waves, xl);
-  auto it = cache.find(key);
-  if (it != cache.end()) return it->second;
-  return cache.emplace(key, occupancy_res(rows, waves, xl)).first->second;
+  return tb_device_memo(TbMemo::kResidentOccupancy, rows, waves, xl, occupancy_res);
 }
-
-struct ResPlan {
-  int rows = 0, waves = 0, units = 0;
-};
 
 int res_xl(int variant, const TbTuning& tune) {
   // Mixed lane shifts unless a forced variant asks for DPP (variant -1 is the
@@ -100,34 +81,14 @@ int res_xl(int variant, const TbTuning& tune) {
   return variant >= 0 && (variant & tbv::kTileDpp) ? 0 : 2;
 }
 
-// The shape with the lowest step estimate (tile_step_estimate) among those
-// whose tiles are all co-resident (one dispatch round; the occupancy of the
-// resident instantiation itself, bounded by its VGPR granule).
-ResPlan plan_res(const Box& box, int depth, int xl, const TbTuning& tune) {
-  ResPlan best;
-  if (box.empty() || depth < 4 || depth % 2 != 0 || box.c0 % 4 != 0) return best;
-  const int W = tb_strip_width(depth, 4);
-  const int cus = tb_simd_count() / 4;
-  double best_est = 0.0;
-  struct Shape {
-    int rows, waves;
-  };
-  static constexpr Shape kShapes[] = {{12, 8}, {13, 8}, {14, 8}, {16, 8}, {20, 8}, {24, 8}, {12, 16}, {20, 16}};
-  for (const Shape& sh : kShapes) {
-    if (tune.tile_rows > 0 && sh.rows != tune.tile_rows) continue;
-    if (tune.tile_waves > 0 && sh.waves != tune.tile_waves) continue;
-    const int64_t hmax = int64_t(sh.waves) * sh.rows - 2 * int64_t(depth);
-    if (hmax < std::max(depth, 4)) continue;
-    const int64_t units = ceil_div(box.cols(), W) * ceil_div(box.rows(), hmax);
-    const int occ = cached_occupancy_res(sh.rows, sh.waves, xl);
-    if (occ <= 0 || units > int64_t(cus) * occ) continue;
-    const double est = tile_step_estimate(units, cus, occ, sh.rows, sh.waves);
-    if (best.rows == 0 || est < best_est) {
-      best_est = est;
-      best = ResPlan{sh.rows, sh.waves, int(units)};
-    }
-  }
-  return best;
+// The shape with the lowest step estimate among those whose tiles are all
+// co-resident (one dispatch round; the occupancy of the resident
+// instantiation itself, bounded by its VGPR granule).
+TilePlan plan_res(const Box& box, int depth, int xl, const TbTuning& tune) {
+  return resident_tile_plan(
+      box, depth, tb_simd_count() / 4,
+      [&](int i) { return cached_occupancy_res(kResidentShapes[i].rows, kResidentShapes[i].waves, xl); },
+      tune.tile_rows, tune.tile_waves);
 }
 }  // namespace
 
@@ -136,25 +97,17 @@ ResPlan plan_res(const Box& box, int depth, int xl, const TbTuning& tune) {
 namespace heat::gpu {
 
 bool tb_resident_fits(const Box& box, int depth, int variant) {
-  using namespace tbw;
-  const TbTuning tune = tb_tuning();
-  const ResPlan pl = plan_res(box, depth, res_xl(variant, tune), tune);
-  if (pl.rows == 0) return false;
-  // Every tile but the last of a strip (and every strip but the last) must
-  // be at least K rows (KK columns) deep: a ghost ring comes from the
-  // direct neighbours only.
-  const int64_t hmax = int64_t(pl.waves) * pl.rows - 2 * int64_t(depth);
-  const int64_t n = ceil_div(box.rows(), hmax);
-  return ceil_div(box.rows(), n) >= depth;
+  return tb_resident_shape(box, depth, variant) != 0;
 }
 
 int tb_resident_shape(const Box& box, int depth, int variant) {
   using namespace tbw;
   const TbTuning tune = tb_tuning();
-  const ResPlan pl = plan_res(box, depth, res_xl(variant, tune), tune);
-  if (pl.rows == 0) return 0;
-  const int64_t hmax = int64_t(pl.waves) * pl.rows - 2 * int64_t(depth);
-  if (ceil_div(box.rows(), ceil_div(box.rows(), hmax)) < depth) return 0;
+  const TilePlan pl = plan_res(box, depth, res_xl(variant, tune), tune);
+  // Every tile but the last of a strip (and every strip but the last) must
+  // be at least K rows (KK columns) deep: a ghost ring comes from the
+  // direct neighbours only.
+  if (pl.rows == 0 || !tiles_at_least_depth(box.rows(), pl, depth)) return 0;
   return res_shape(pl.rows, pl.waves);
 }
 
@@ -166,14 +119,13 @@ void tb_resident_step(const float* src, float* dst, const StencilGeom& g, const 
   HEAT_CHECK(passes >= 2, "a resident launch spans >= 2 passes (%d)", passes);
   const TbTuning tune = tb_tuning();
   int xl = res_xl(variant, tune);
-  const ResPlan pl = plan_res(box, depth, xl, tune);
+  const TilePlan pl = plan_res(box, depth, xl, tune);
   HEAT_CHECK(pl.rows > 0, "resident tiles do not fit box %lldx%lld at depth %d",
              (long long)box.rows(), (long long)box.cols(), depth);
-  HEAT_CHECK(pl.units <= xb.max_tiles, "%d resident tiles, flag buffer holds %d", pl.units,
-             xb.max_tiles);
+  const int units = int(pl.units);  // one dispatch round
+  HEAT_CHECK(units <= xb.max_tiles, "%d resident tiles, flag buffer holds %d", units, xb.max_tiles);
   HEAT_CHECK(xb.bytes < (int64_t(1) << 31), "exchange field of %lld bytes (32-bit offsets)",
              (long long)xb.bytes);
-  const int64_t hmax = int64_t(pl.waves) * pl.rows - 2 * int64_t(depth);
   ResArgs ra{};
   TbArgs& a = ra.a;
   a.src = src;
@@ -215,18 +167,10 @@ void tb_resident_step(const float* src, float* dst, const StencilGeom& g, const 
   a.g = g;
   a.flags = (variant < 0 || (variant & tbv::kXcdGroups)) ? tbdetail::kTbXcdGroups : 0;
   TbBox& t = a.box[0];
-  t.r0 = box.r0;
-  t.r1 = box.r1;
-  t.c0 = box.c0;
-  t.c1 = box.c1;
-  t.nstrips = int(ceil_div(box.cols(), tb_strip_width(depth, 4)));
-  t.nchunks = int(ceil_div(box.rows(), hmax));
-  t.chunk_len = int(ceil_div(box.rows(), int64_t(t.nchunks)));
+  a.total_waves = int(tile_fill_box(t, box, depth, pl, 0));
   HEAT_CHECK(t.chunk_len >= depth, "resident tiles of %d rows at depth %d", t.chunk_len, depth);
-  t.wave_begin = 0;
   a.nbox = 1;
-  a.total_waves = t.nstrips * t.nchunks;
-  HEAT_CHECK(a.total_waves == pl.units, "resident plan %d != %d tiles", pl.units, a.total_waves);
+  HEAT_CHECK(a.total_waves == units, "resident plan %d != %d tiles", units, a.total_waves);
   ra.passes = passes;
   ra.depth = depth;
   ra.xbase[0] = xb.base[0];
@@ -242,16 +186,12 @@ void tb_resident_step(const float* src, float* dst, const StencilGeom& g, const 
   ra.diag = tune.res_diag;
   // The flags and the completion counter are zero: zeroed once when the
   // buffers are allocated, then by the last tile of every launch.
-  if (const char* e = std::getenv("HEAT_TB_TRACE"); e && *e && *e != '0') {
-    static std::mutex mu;
-    static std::set<std::string> seen;
+  if (tb_trace_enabled()) {
     char line[200];
-    std::snprintf(line, sizeof line, "[heat tb] resident depth %d passes %d rows %d waves %d xl %d tiles %d\n",
-                  depth, passes, pl.rows, pl.waves, xl, pl.units);
-    std::lock_guard<std::mutex> lk(mu);
-    if (seen.insert(line).second) std::fputs(line, stderr);
+    resident_trace_line(line, depth, passes, pl, xl);
+    tb_trace_once(line);
   }
-  HEAT_CHECK(launch_res(ra, pl.rows, pl.waves, xl, pl.units, st), "resident %dx%d not built",
+  HEAT_CHECK(launch_res(ra, pl.rows, pl.waves, xl, units, st), "resident %dx%d not built",
              pl.rows, pl.waves);
   HIP_CHECK(hipGetLastError());
 }

@@ -1,5 +1,6 @@
 // Process topology / decomposition (see topology.hpp for the reference map).
 #include "heat/plan.hpp"
+#include "heat/tb_plan.hpp"
 #include "heat/topology.hpp"
 
 #include <algorithm>
@@ -191,39 +192,11 @@ int resident_halo_passes(const Cart& cart, int64_t nx, int64_t ny, int depth, in
 }
 
 int resident_shape_static(const Box& box, int depth, int cus) {
-  // (rows per wave, waves per workgroup, workgroups per CU), plan_res's order.
-  static constexpr int kShapes[][3] = {{12, 8, 2}, {13, 8, 2}, {14, 8, 2}, {16, 8, 2},
-                                       {20, 8, 1}, {24, 8, 1}, {12, 16, 1}, {20, 16, 1}};
-  if (box.empty() || depth < 4 || depth % 2 != 0 || box.c0 % 4 != 0) return 0;
-  const int64_t W = 256 - 2 * round_up(int64_t(depth), 4);
-  // tb_tile.hpp tile_step_estimate: waves per SIMD of the busiest CU x rows.
-  auto estimate = [&](int64_t units, int occ, int rows, int waves) {
-    const int64_t cap = int64_t(cus) * occ, full = (units - 1) / cap;
-    const int64_t busiest = (units - full * cap + cus - 1) / cus;
-    auto cost = [&](int64_t tiles) {
-      const double wps = double(tiles * waves) / 4.0;
-      return wps * rows * (wps >= 4.0 ? 2.7 : 3.1);
-    };
-    return double(full) * cost(occ) + cost(busiest);
-  };
-  int best = 0;
-  double best_est = 0.0;
-  int64_t best_hmax = 0;
-  for (const auto& s : kShapes) {
-    const int64_t hmax = int64_t(s[0]) * s[1] - 2 * int64_t(depth);
-    if (hmax < std::max(depth, 4)) continue;
-    const int64_t units = ceil_div(box.cols(), W) * ceil_div(box.rows(), hmax);
-    if (units > int64_t(cus) * s[2]) continue;
-    const double est = estimate(units, s[2], s[0], s[1]);
-    if (best == 0 || est < best_est) {
-      best = res_shape(s[0], s[1]);
-      best_est = est;
-      best_hmax = hmax;
-    }
-  }
-  // tb_resident_fits: every tile but the last of a strip at least K rows.
-  if (best != 0 && ceil_div(box.rows(), ceil_div(box.rows(), best_hmax)) < depth) return 0;
-  return best;
+  using namespace gpu::tbw;
+  const TilePlan pl =
+      resident_tile_plan(box, depth, cus, [](int i) { return kResidentOccGfx950[i]; });
+  if (pl.rows == 0 || !tiles_at_least_depth(box.rows(), pl, depth)) return 0;
+  return res_shape(pl.rows, pl.waves);
 }
 
 }  // namespace heat

@@ -84,13 +84,14 @@ STRIP_COLS = 232  # useful columns per 256-column strip at depth 12
 CUS = 256
 
 # The resident planner's shapes (rows per wave, waves, workgroups per CU at
-# their VGPR budget): csrc/kernels/tb_resident.hip plan_res.
+# their VGPR budget): csrc/include/heat/tb_plan.hpp kResidentShapes and
+# kResidentOccGfx950.
 RES_SHAPES = [(12, 8, 2), (13, 8, 2), (14, 8, 2), (16, 8, 2), (20, 8, 1), (24, 8, 1),
               (12, 16, 1), (20, 16, 1)]
 
 
 def _tile_step_estimate(units: int, occ: int, rows: int, waves: int) -> float:
-    """csrc/kernels/tb_tile.hpp tile_step_estimate (the planner's choice)."""
+    """csrc/include/heat/tb_plan.hpp tile_step_estimate (the planner's choice)."""
     cap = CUS * occ
     full = (units - 1) // cap
     busiest = (units - full * cap + CUS - 1) // CUS
@@ -103,8 +104,9 @@ def _tile_step_estimate(units: int, occ: int, rows: int, waves: int) -> float:
 
 def resident_shape(rows: int, cols: int, depth: int = 12) -> tuple:
     """The resident planner's (rows per wave, waves) for a rows x cols box, or
-    None without a one-round plan (csrc/src/topology.cpp
-    resident_shape_static, tb_resident.hip plan_res)."""
+    None without a one-round plan: a Python mirror of
+    csrc/include/heat/tb_plan.hpp resident_tile_plan with tiles_at_least_depth
+    (what resident_shape_static and the device planner both call)."""
     if rows <= 0 or cols <= 0 or depth < 4 or depth % 2:
         return None
     strips = math.ceil(cols / (256 - 2 * ((depth + 3) // 4 * 4)))

@@ -23,10 +23,10 @@ def test_variant_flags_match_the_engine():
     V = ops.TbVariant
     assert int(V.DEFAULT) == 23 and int(V.DEFAULT_DEEP) == 2071
     assert V.DEFAULT_DEEP & V.SPLIT and V.DEFAULT & V.SCALAR and (V.DEFAULT & 3) == V.RAMP
-    # csrc/include/heat/kernels.hpp tbv:: values
+    # csrc/include/heat/tb_plan.hpp tbv:: values
     import re
     from parallel_heat_amd import _native
-    src = (_native.REPO_DIR / "csrc" / "include" / "heat" / "kernels.hpp").read_text()
+    src = (_native.REPO_DIR / "csrc" / "include" / "heat" / "tb_plan.hpp").read_text()
     names = {"kRing3": V.RING3, "kRing4": V.RING4, "kRing2": V.RING2, "kRamp": V.RAMP,
              "kScalar": V.SCALAR, "kXcdGroups": V.XCD_GROUPS, "kAltDirection": V.ALT_DIRECTION,
              "kFloat2": V.FLOAT2, "kForceAgePairs": V.FORCE_AGE_PAIRS, "kSplit": V.SPLIT,
