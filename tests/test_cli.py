@@ -11,6 +11,7 @@ import pytest
 from parallel_heat_amd import HeatConfig, HeatSolver, _native
 from parallel_heat_amd.utils import io as hio
 
+from . import ref_golden as RG
 from .dist_worker import free_port
 
 HEAT = str(_native.CLI_PATH)
@@ -22,6 +23,22 @@ def heat(args, cwd, env=None, check=True):
     e.update(env or {})
     return subprocess.run([HEAT] + args, cwd=cwd, env=e, capture_output=True, text=True,
                           check=check, timeout=300)
+
+
+def heat_ranks(args, cwd, world):
+    """`heat` as `world` processes, CPU ranks over TCP on 127.0.0.1 (appends
+    --transport tcp --port); every rank must exit 0.  [(stdout, stderr)] by rank."""
+    base = list(args) + ["--transport", "tcp", "--port", str(free_port())]
+    procs = []
+    for r in range(world):
+        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r),
+                   MASTER_ADDR="127.0.0.1")
+        procs.append(subprocess.Popen([HEAT] + base, cwd=cwd, env=env,
+                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
+    outs = [p.communicate(timeout=300) for p in procs]
+    for p, (o, e) in zip(procs, outs):
+        assert p.returncode == 0, e
+    return outs
 
 
 def reference_grid(nx, ny, steps, **kw):
@@ -43,6 +60,19 @@ def test_cli_mpi_naming_and_lines(tmp_path):
     ref = tmp_path / "ref.dat"
     hio.write_dat(str(ref), g)
     assert (tmp_path / "final_im.dat").read_bytes() == ref.read_bytes()
+    # Against what the reference MPI program itself wrote (tests/golden/mpi_ref):
+    # the initial plate as it stands, and with the program's arithmetic
+    # (--numerics mpi) its lines and its final plate.
+    c = RG.case("20x20_100")
+    RG.assert_file(c, "initial_im.dat", (tmp_path / "initial_im.dat").read_bytes())
+    assert RG.normalised(lines) == RG.expected_lines(c)
+    d = tmp_path / "numerics_mpi"
+    d.mkdir()
+    q = heat(["--backend", "cpu", "--nx", "20", "--ny", "20", "--steps", "100", "--naming", "mpi",
+              "--numerics", "mpi"], d)
+    assert RG.normalised(q.stdout.splitlines()) == RG.expected_lines(c)
+    for name in ("initial_im.dat", "final_im.dat"):
+        RG.assert_file(c, name, (d / name).read_bytes())
 
 
 def test_cli_cuda_naming_and_convergence(tmp_path):
@@ -71,19 +101,9 @@ def test_cli_json_and_checksum(tmp_path):
 @pytest.mark.parametrize("world,extra", [(2, []), (4, []), (4, ["--decomp", "rows", "--tb-depth", "3"]),
                                          (3, ["--px", "1", "--py", "3"])])
 def test_cli_tcp_multiprocess_invariance(tmp_path, world, extra):
-    port = free_port()
     base = ["--backend", "cpu", "--nx", "41", "--ny", "39", "--steps", "57", "--init", "random",
-            "--seed", "3", "--out", "g.bin", "--out-format", "bin", "--transport", "tcp",
-            "--port", str(port)] + extra
-    procs = []
-    for r in range(world):
-        env = dict(os.environ, RANK=str(r), WORLD_SIZE=str(world), LOCAL_RANK=str(r),
-                   MASTER_ADDR="127.0.0.1")
-        procs.append(subprocess.Popen([HEAT] + base, cwd=tmp_path, env=env,
-                                      stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True))
-    outs = [p.communicate(timeout=300) for p in procs]
-    for p, (o, e) in zip(procs, outs):
-        assert p.returncode == 0, e
+            "--seed", "3", "--out", "g.bin", "--out-format", "bin"] + extra
+    heat_ranks(base, tmp_path, world)
     g, h = hio.read_bin(str(tmp_path / "g.bin"))
     assert h["step"] == 57
     ref = reference_grid(41, 39, 57, init="random", seed=3)
